@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - sim-us/s of the emulation hot path on MI355X (driver contract).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload north_star|cfg2|cfg3|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload north_star|cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Default workload = the north-star target (BASELINE.json): the 14-atom triangular register
@@ -31,12 +31,20 @@ Default workload = the north-star target (BASELINE.json): the 14-atom triangular
   parity_max_abs   sequence 0 of the timed batch against the tight-oracle fixture of the same register (the line is
                    not printed beyond 1e-7).
   collective       N > 1: backend, world size, PCI bus ids of the ranks' devices (all-gathered), an all-reduce of ones.
+
+--dump-outputs DIR writes, after the run, what the primary workload's LAST timed step computed (rank 0) as float64
+DIR/<name>.npy: `occupations` (the step's occupation sums: one per atom, then the squared norm / trace) and
+`final_state` (real / imaginary pairs; at most 32 MiB: a fixed seeded sample of 2^14-amplitude pieces, whose indices are
+`final_state_pieces`) - cfg4: `histograms`, `mean_occupations`, `mean_norm`.  The inputs are seeded, so two builds run
+with the same arguments can be compared output for output (`bench_outputs/` is git-ignored for the purpose): the state
+bit for bit, the occupation sums to rounding (the device reduces them with fp64 atomics, ~1e-14 from run to run).
 """
 from __future__ import annotations
 
 import argparse
 import dataclasses
 import json
+import math
 import os
 import sys
 import time
@@ -208,6 +216,33 @@ def timed_run(eng, state_fn, t0, t1, steps, warmup, dist=None, torch=None, **opt
     eng.set_kernel_timing(False)
     timed_run.last_state = st
     return dt / steps, stats, kms, kl, occ
+
+
+DUMP_STATE_BYTES = 32 << 20  # --dump-outputs: at most this much of the final state (float64 real / imaginary pairs)
+DUMP_PIECE = 1 << 14         # ... sampled in pieces of this many amplitudes: a 14-atom ket, a row of a 14-atom density matrix
+DUMP_SEED = 0
+
+
+def output_sample(torch, state, occ):
+    """What the timed path handed back in its LAST timed step, as float64 host arrays (--dump-outputs): the occupation
+    sums of the step and the final state - whole if it fits DUMP_STATE_BYTES, else a fixed seeded sample of its pieces
+    (the state viewed as rows of gcd(last dimension, DUMP_PIECE) amplitudes; `final_state_pieces` = the rows kept)."""
+    piece = math.gcd(int(state.shape[-1]), DUMP_PIECE)
+    rows = state.reshape(-1, piece)
+    keep = max(1, DUMP_STATE_BYTES // (piece * 16))
+    idx = np.arange(rows.shape[0])
+    if rows.shape[0] > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows.shape[0], keep, replace=False))
+    sample = rows.index_select(0, torch.as_tensor(idx, device=rows.device)).cpu()
+    sample = torch.view_as_real(sample) if sample.is_complex() else sample
+    return {"final_state": sample.to(torch.float64).numpy(), "final_state_pieces": idx.astype(np.float64),
+            "occupations": occ.detach().to(torch.float64).cpu().numpy()}
+
+
+def write_outputs(path, outputs):
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def measured_traffic(key):
@@ -508,6 +543,8 @@ def cfg4_line(n_traj, steps, warmup, dist, torch, n_gpus, common):
         tmax = torch.tensor([sec], dtype=torch.float64, device="cuda")
         all_reduce(dist, tmax, dist.ReduceOp.MAX)
         sec = float(tmax.item())
+    # what the last timed pass handed back (--dump-outputs)
+    cfg4_line.last_outputs = {k: np.asarray(res[k], dtype=np.float64) for k in ("histograms", "mean_occupations", "mean_norm")}
     # the same with the ensemble density matrix (density_matrix_aggregator: the 268-MB mean of |psi><psi|
     # at both evaluation times, formed on the device and all-reduced there)
     one_pass(200, True)
@@ -612,10 +649,17 @@ def device_copy_bandwidth(torch):
     return 2.0 * n * 8 / sec / 1e9
 
 
+def _positive_int(text):
+    value = int(text)
+    if value < 1:
+        raise argparse.ArgumentTypeError(f"{text}: at least one step")
+    return value
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=_positive_int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=256, help="independent sequences per GPU")
     ap.add_argument("--workload", default="north_star")
@@ -635,6 +679,8 @@ def main() -> None:
                     help="north star: keep the batch on k_ket instead of the split-operator kernel (A/B runs)")
     ap.add_argument("--split-turns", action="store_true",
                     help="north star: the round-3 kernel k_split14_loop instead of k_split_reg (A/B runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -711,6 +757,7 @@ def main() -> None:
         if args.no_ket or args.no_split14 or args.split_turns:
             eng.set_path(False, no_ket=args.no_ket, no_split14=args.no_split14, split_turns=args.split_turns)
         sec, stats, kms, kl, occ = timed_run(eng, eng.new_state, 0.0, T_SEQ_US, args.steps, args.warmup, dist, torch)
+        outputs = output_sample(torch, timed_run.last_timed_state, occ) if args.dump_outputs else None
         value = n_gpus * B * T_SEQ_US / sec
         ket = stats["n_launches"] == 1
         split14 = not ket and not args.no_ket and stats["reserved"][0] > 0.0
@@ -863,6 +910,7 @@ def main() -> None:
         n, B = 12, args.batch
         eng = Engine.from_problems([chain_problem(n)] * B, mode="sesolve")
         sec, stats, kms, kl, occ = timed_run(eng, eng.new_state, 0.0, T_SEQ_US, args.steps, args.warmup, dist, torch)
+        outputs = output_sample(torch, timed_run.last_timed_state, occ) if args.dump_outputs else None
         out = {
             "metric": "sim-us/sec, 12-atom Rydberg anneal sequence, sesolve fp64 (aggregate over sequences)",
             "value": n_gpus * B * T_SEQ_US / sec, **common, "ms_per_step": sec * 1e3,
@@ -880,6 +928,7 @@ def main() -> None:
         eng.close()
     elif args.workload == "cfg4":
         out = cfg4_line(args.trajectories, args.steps, args.warmup, dist, torch, n_gpus, common)
+        outputs = cfg4_line.last_outputs
         extras_ok = False
         args.no_cpu = True
     elif args.workload in ("cfg3", "cfg5"):
@@ -907,6 +956,7 @@ def main() -> None:
             eng.evolve(psi1, 0.0, t0)  # the slice starts from the state the sequence has reached at t0
             state_fn = psi1.clone
         sec, stats, kms, kl, occ = timed_run(eng, state_fn, t0, t1, args.steps, args.warmup, dist, torch, **mopt)
+        outputs = output_sample(torch, timed_run.last_timed_state, occ) if args.dump_outputs else None
         if args.workload == "cfg3" and not args.no_ket:
             roof = roofline_valu(2.0**14, 2.0**15, stats["n_applications"], KSPLITREG_FLOPS_PER_AMP_STAGE, kms, kl, kname, "cfg3:k_split_reg",
                                  algorithmic_flops_per_amp_stage=SPLIT_ALGORITHMIC_FLOPS_PER_AMP_STAGE)
@@ -1083,6 +1133,9 @@ def main() -> None:
         out["device_copy_GBps"] = bw
         if out.get("lindblad", {}).get("roofline", {}).get("hbm_equivalent_GBps"):
             out["lindblad"]["hbm_equivalent_over_copy_bandwidth"] = out["lindblad"]["roofline"]["hbm_equivalent_GBps"] / bw
+
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, outputs)
 
     if rank == 0:
         out["cpu_baseline"] = cpu_result

@@ -126,3 +126,23 @@ def test_the_rccl_branch_runs_at_world_size_one():
     # ... and it is the serial ensemble (rank 0 owns every draw)
     _, serial = _bench(1, "--workload", "cfg4", "--trajectories", "48")
     assert np.allclose(det["config"]["mean_occupations_final"], serial["config"]["mean_occupations_final"], atol=1e-12)
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: what the timed path computed in its last step, as float64 .npy - the final kets (16 x 2^14
+    amplitudes fit the budget whole) and the step's occupation sums; sequence 0 is the nominal sequence of the
+    tight-oracle fixture, so the dumped ket is checked against it."""
+    from pulser_amd import problem as P
+
+    dump = tmp_path / "out"
+    line, det = _bench(1, "--no-legs", "--batch", "16", "--dump-outputs", str(dump))
+    assert line["steps"] == 1
+    psi = np.load(dump / "final_state.npy")
+    assert psi.dtype == np.float64 and psi.shape == (16, 2**14, 2)
+    assert np.array_equal(np.load(dump / "final_state_pieces.npy"), np.arange(16.0))
+    _, fx = P.load_problem(os.path.join(ROOT, "tests", "golden", "ns_tri14_anneal.npz"))
+    err = np.max(np.abs(psi[0, :, 0] + 1j * psi[0, :, 1] - np.asarray(fx["oracle_states_tight"])[-1]))
+    assert err < 1e-7 and err == pytest.approx(det["parity_max_abs"], rel=1e-12)
+    occ = np.load(dump / "occupations.npy")
+    assert occ.dtype == np.float64 and occ.shape == (15,)
+    assert np.allclose(occ / 16, det["ensemble_mean_occupations"] + [det["ensemble_mean_norm"]], rtol=0, atol=1e-14)

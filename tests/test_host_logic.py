@@ -1706,6 +1706,37 @@ def test_bench_driver_line_is_short_scalar_and_round_trips():
     assert line["roofline"] is None and line["cpu_baseline"] is None
 
 
+
+def test_bench_output_sample_is_seeded_bounded_and_float64(tmp_path):
+    """bench.py --dump-outputs: the final state of the last timed step whole when it fits the budget, else the same
+    seeded sample of 2^14-amplitude pieces every run (the 256 x 14-atom headline batch: 128 kets); float64 files only,
+    together below 64 MB, and the pieces kept are the state's own rows."""
+    import sys
+
+    import torch
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+
+    g = torch.Generator().manual_seed(3)
+    occ = torch.rand(15, dtype=torch.float64, generator=g)
+    small = torch.randn(16, 4096, dtype=torch.complex128, generator=g)
+    out = bench.output_sample(torch, small, occ)
+    assert np.array_equal(out["final_state"][..., 0] + 1j * out["final_state"][..., 1], small.numpy())
+    assert np.array_equal(out["final_state_pieces"], np.arange(16)) and np.array_equal(out["occupations"], occ.numpy())
+    big = torch.randn(256, 2**14, dtype=torch.complex128, generator=g)
+    out = bench.output_sample(torch, big, occ)
+    rows = out["final_state_pieces"].astype(int)
+    assert out["final_state"].shape == (128, 2**14, 2) and len(np.unique(rows)) == 128
+    assert np.array_equal(out["final_state"][..., 0] + 1j * out["final_state"][..., 1], big.numpy()[rows])
+    assert np.array_equal(bench.output_sample(torch, big * 2, occ)["final_state_pieces"], out["final_state_pieces"])
+    bench.write_outputs(str(tmp_path / "dump"), out)
+    files = sorted((tmp_path / "dump").iterdir())
+    assert [f.name for f in files] == ["final_state.npy", "final_state_pieces.npy", "occupations.npy"]
+    assert sum(f.stat().st_size for f in files) <= 64e6
+    assert all(np.load(f).dtype == np.float64 for f in files)
+
 def test_c_replay_equals_the_numpy_replay():
     """ryd_replay_samples (host_replay.hpp; host arithmetic only, so it runs without a GPU): weights, cumulative sums,
     searchsorted and the SPAM flips of a block of states in the same IEEE operations as the NumPy replay
