@@ -79,7 +79,17 @@ extern "C" int ryd_general_add_term(ryd_handle* h, int64_t nnz, const int32_t* r
   t.conj = conj;
   t.scale = std::complex<double>(scale_re, scale_im);
   t.row_norm = row_norm;
-  t.step_norm = row_norm;
+  {
+    // the term's own infinity norm (largest row sum of |values|): the caller's `row_norm` may be a jointly tightened
+    // share (pulser_amd/general.py: _tighten_static_norms) that must not shorten the CF4 steps
+    double own = 0.0;
+    for (size_t r = 0; r < h->dim; ++r) {
+      double s = 0.0;
+      for (int64_t e = std::max<int64_t>(row_ptr[r], 0); e < std::min<int64_t>(row_ptr[r + 1], nnz); ++e) s += std::hypot(val[2 * e], val[2 * e + 1]);
+      own = std::max(own, s);
+    }
+    t.step_norm = std::max(row_norm, own);
+  }
   HIPCHK(hipMalloc((void**)&t.dev.row_ptr, (h->dim + 1) * sizeof(int)));
   HIPCHK(hipMalloc((void**)&t.dev.col, std::max<int64_t>(nnz, 1) * sizeof(int)));
   HIPCHK(hipMalloc((void**)&t.dev.val, std::max<int64_t>(nnz, 1) * sizeof(cplx)));
@@ -205,7 +215,12 @@ extern "C" int ryd_general_add_diag_term(ryd_handle* h, const double* values, in
   t.conj = conj;
   t.scale = std::complex<double>(scale_re, scale_im);
   t.row_norm = row_norm;
-  t.step_norm = row_norm;
+  {
+    // the term's own infinity norm max_i |values[i]| (see ryd_general_add_term)
+    double own = 0.0;
+    for (size_t i = 0; i < h->dim; ++i) own = std::max(own, std::hypot(values[2 * i], values[2 * i + 1]));
+    t.step_norm = std::max(row_norm, own);
+  }
   t.dev.kind = 2;
   HIPCHK(hipMalloc((void**)&t.dev.val, h->dim * sizeof(cplx)));
   HIPCHK(hipMemcpy((void*)t.dev.val, values, h->dim * sizeof(cplx), hipMemcpyHostToDevice));

@@ -233,6 +233,11 @@ def test_reference_golden_counters_all_basis_end_to_end(k):
     assert tr2 < 1 and not np.isclose(tr2, 1)
 
 
+# largest max-abs distance of the noisy_xy_* per-trajectory oracle states (default zvode options) from the same
+# trajectories integrated at qp.TIGHT, over all six cases and every trajectory
+XY_ORACLE_DEFAULT_GAP = 4.7e-4  # (noisy_xy_2, leakage: 4.69e-4; the others 6e-5 .. 2.3e-4)
+
+
 @pytest.mark.parametrize("k", range(6))
 def test_reference_golden_counters_xy_end_to_end(k):
     """test_simulation.py:1536-1690 (MESOLVER cases) with the real solver: XY
@@ -241,9 +246,26 @@ def test_reference_golden_counters_xy_end_to_end(k):
     from test_host_logic import _xy_emulator
 
     emu, extra = _xy_emulator(k)
+    finals = []
+    runs = emu._noisy_runs
+
+    def spy(*a, **kw):  # the per-trajectory results the sampled Counter is built from, in trajectory order
+        for res, reps in runs(*a, **kw):
+            finals.append(np.asarray(res.states[-1]))
+            yield res, reps
+
+    emu._noisy_runs = spy
     with pytest.warns(DeprecationWarning):
         r = emu.run()
     assert r.sample_final_state() == Counter(extra["reference_golden_counter"])
+    # State-level check: every trajectory's final rho against the oracle's.  Those states were integrated with the
+    # reference's DEFAULT solver options (make_fixtures.py: gen_noisy_xy, qp.default_options), not qp.TIGHT; they sit
+    # up to XY_ORACLE_DEFAULT_GAP from the tight solution of the same trajectories, the bar is that gap plus margin.
+    ref = np.asarray(extra["oracle_traj_lookup_states"])
+    assert len(finals) == len(ref)
+    err = max(float(np.max(np.abs(f - s))) for f, s in zip(finals, ref))
+    print(f"noisy_xy_{k}: max |emulator rho - oracle rho| over {len(ref)} trajectories = {err:.2e}")
+    assert err < 2.0 * XY_ORACLE_DEFAULT_GAP, err
 
 
 def test_get_hamiltonian_reference_goldens():
