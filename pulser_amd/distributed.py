@@ -25,6 +25,7 @@ GPUs, ``gloo`` in the CPU tests.
 from __future__ import annotations
 
 import os
+import threading
 from collections import Counter
 from typing import Any, Callable, Sequence
 
@@ -246,19 +247,40 @@ def _broadcast_array(dist: Any, arr: np.ndarray | None, shape: tuple[int, ...], 
     return t.cpu().numpy()
 
 
-# pinned staging buffers of the sampling replay, kept between ensembles (allocating 67 MB of pinned host memory costs
-# more than copying it); one buffer per (shape, dtype), at most two kept
-_PINNED_CACHE: dict[tuple, Any] = {}
+class StagingPool:
+    """Pinned staging buffers of the sampling replay, kept between ensembles (allocating 67 MB of pinned host memory costs
+    more than copying it).  A buffer is checked out by one caller and handed to no one else until it is released; at most
+    ``max_idle`` released buffers are kept (oldest dropped first), a buffer in use is never dropped.  ``alloc(shape,
+    dtype)`` makes a new buffer (pinned host memory by default; tests pass ``torch.empty``)."""
+
+    def __init__(self, alloc: Callable[[tuple, Any], Any] | None = None, max_idle: int = 2) -> None:
+        self._alloc = alloc or _alloc_pinned
+        self._max_idle = max_idle
+        self._idle: list[tuple[tuple, Any]] = []  # (key, buffer), oldest first
+        self._lock = threading.Lock()
+
+    def checkout(self, shape: Sequence[int], dtype: Any) -> Any:
+        key = (tuple(shape), str(dtype))
+        with self._lock:
+            for k, (idle_key, buf) in enumerate(self._idle):
+                if idle_key == key:
+                    del self._idle[k]
+                    return buf
+        return self._alloc(key[0], dtype)
+
+    def release(self, buf: Any) -> None:
+        with self._lock:
+            self._idle.append(((tuple(buf.shape), str(buf.dtype)), buf))
+            del self._idle[: max(0, len(self._idle) - self._max_idle)]
 
 
-def _pinned_like(torch: Any, dev_t: Any) -> Any:
-    key = (tuple(dev_t.shape), str(dev_t.dtype))
-    buf = _PINNED_CACHE.get(key)
-    if buf is None:
-        while len(_PINNED_CACHE) >= 2:
-            _PINNED_CACHE.pop(next(iter(_PINNED_CACHE)))
-        buf = _PINNED_CACHE[key] = torch.empty(key[0], dtype=dev_t.dtype, pin_memory=True)
-    return buf
+def _alloc_pinned(shape: tuple, dtype: Any) -> Any:
+    import torch
+
+    return torch.empty(shape, dtype=dtype, pin_memory=True)
+
+
+_STAGING = StagingPool()
 
 
 def run_ensemble(
@@ -385,8 +407,8 @@ def run_ensemble(
     # the C replay (ryd_replay_samples: the same arithmetic on host threads, outside the GIL); PULSER_AMD_NUMPY_REPLAY=1
     # keeps the NumPy replay (A/B, and what the CPU tests compare it with)
     native_replay = fast and not os.environ.get("PULSER_AMD_NUMPY_REPLAY")
-    pinned: Any = None       # the replay worker's pinned staging buffer and copy stream (one worker: used block after block)
-    copy_stream: Any = None
+    pinned: Any = None       # the replay worker's pinned staging buffer (this call's own, checked out of _STAGING) and copy
+    copy_stream: Any = None  # stream (one worker: used block after block)
     pool = None
     pending: list[Any] = []
     try:
@@ -463,7 +485,10 @@ def run_ensemble(
                         nonlocal pinned, copy_stream
                         if copy_stream is None:
                             copy_stream = _t.cuda.Stream(device=dev_all.device)
-                        pinned = _pinned_like(_t, dev_all)
+                        if pinned is None or pinned.shape != dev_all.shape:  # (a shorter last block: another buffer)
+                            if pinned is not None:
+                                _STAGING.release(pinned)
+                            pinned = _STAGING.checkout(dev_all.shape, dev_all.dtype)
                         with _t.cuda.stream(copy_stream):
                             copy_stream.wait_event(ready)
                             pinned.copy_(dev_all, non_blocking=True)
@@ -520,6 +545,8 @@ def run_ensemble(
             fut.cancel()
         if pool is not None:
             pool.shutdown(wait=True)
+        if pinned is not None:  # no replay can read it any more
+            _STAGING.release(pinned)
         if lower_pool is not None:
             lower_pool.shutdown(wait=True)
     # -- the one collective per accumulator: sum over ranks -----------------

@@ -171,12 +171,16 @@ class SnapshotStore:
     store is registered (weakly), and before a new one is added the OLDEST stores are spilled to the host until the
     retained device bytes fit ``device_budget_bytes()`` (default 1/8 of the device's memory; ``PULSER_AMD_SNAPSHOT_GB``
     overrides).  Spilling changes where a state is read from, never what is read.  ``spill_all()`` / a results object's
-    ``to_host()`` move everything explicitly."""
+    ``to_host()`` move everything explicitly.
+
+    **Locking.**  ``_registry_lock`` guards the registry and is held only to pick the stores to spill; the spills run after
+    it is released.  Each store's own ``_lock`` guards its ``_dev`` / ``_host``: a read is wholly before or after a spill."""
 
     _live: "list[weakref.ref[SnapshotStore]]" = []   # registration order = age
-    _lock = threading.Lock()
+    _registry_lock = threading.Lock()  # taken before a store's own lock, never after
 
     def __init__(self, tensor: Any, bulk_after: int = 16) -> None:
+        self._lock = threading.RLock()
         self._dev = tensor
         self._host: list[np.ndarray] | None = None  # after fetch_all: one array per evaluation time
         self._reads = 0
@@ -197,68 +201,77 @@ class SnapshotStore:
             return 8 * 2**30
 
     def device_bytes(self) -> int:
-        dev = self._dev
+        with self._lock:
+            dev = self._dev
         return 0 if dev is None else int(getattr(dev, "nbytes", 0))
 
     @classmethod
     def _alive(cls) -> "list[SnapshotStore]":
-        stores = [r() for r in cls._live]
-        cls._live = [r for r, s in zip(cls._live, stores) if s is not None and s._dev is not None]
-        return [s for s in stores if s is not None and s._dev is not None]
+        """The registered stores still on the device, oldest first; drops the others from the registry."""
+        pairs = [(r, r()) for r in cls._live]
+        pairs = [(r, s) for r, s in pairs if s is not None and s._dev is not None]
+        cls._live = [r for r, _ in pairs]
+        return [s for _, s in pairs]
 
     @classmethod
     def retained_device_bytes(cls) -> int:
-        with cls._lock:
+        with cls._registry_lock:
             return sum(s.device_bytes() for s in cls._alive())
 
     def _register(self) -> None:
         cls = type(self)
-        with cls._lock:
+        with cls._registry_lock:
             budget = cls.device_budget_bytes()
             alive = cls._alive()
             held = sum(s.device_bytes() for s in alive) + self.device_bytes()
+            victims = []
             for s in alive:  # oldest first
                 if held <= budget:
                     break
                 held -= s.device_bytes()
-                s.fetch_all()
-            cls._live = [r for r in cls._live if (r() is not None and r()._dev is not None)]
-            cls._live.append(weakref.ref(self))
+                victims.append(s)
+            cls._live = cls._live[len(victims):] + [weakref.ref(self)]  # (the victims are the oldest of `_live`)
+        for s in victims:
+            s.fetch_all()
 
     @classmethod
     def spill_all(cls) -> int:
         """Move every live store to the host (frees their HBM); returns the bytes moved."""
-        with cls._lock:
-            moved = 0
-            for s in cls._alive():
-                moved += s.device_bytes()
-                s.fetch_all()
+        with cls._registry_lock:
+            victims = cls._alive()
             cls._live = []
-            return moved
+        moved = 0
+        for s in victims:
+            moved += s.device_bytes()
+            s.fetch_all()
+        return moved
 
     # -- reads ----------------------------------------------------------------------------------------------------------
     @property
     def device_tensor(self) -> Any:
         """The torch tensor on the GPU (None once everything has been copied to the host)."""
-        return self._dev
+        with self._lock:
+            return self._dev
 
     def fetch_all(self) -> "list[np.ndarray]":
         """Everything to the host: ONE array per evaluation time ([B, dim...]), not one array for the run - a state that
         outlives the run then keeps its own time slice alive and nothing else, without a second copy (round 6: copying
         every state out of one big host array cost 220 ms of page faults when all 3 101 states of a 14-atom run were read)."""
-        if self._host is None:
-            dev = self._dev
-            self._host = [dev[i].cpu().numpy() for i in range(int(dev.shape[0]))]
-            self._dev = None
-        return self._host
+        with self._lock:
+            if self._host is None:
+                dev = self._dev
+                self._host = [dev[i].cpu().numpy() for i in range(int(dev.shape[0]))]
+                self._dev = None
+            return self._host
 
     def get(self, i: int, b: int) -> np.ndarray:
-        if self._host is None:
-            self._reads += 1
-            if self._reads <= self._bulk_after:
-                return self._dev[i, b].cpu().numpy()
-            self.fetch_all()
-        slab = self._host[i]
+        with self._lock:
+            if self._host is None:
+                self._reads += 1
+                if self._reads <= self._bulk_after:
+                    return self._dev[i, b].cpu().numpy()
+                self.fetch_all()
+            slab = self._host[i]
         # one sequence per run: the time slice IS the state (a view of its own array); batched runs copy the entry out so
         # that one kept state does not pin its neighbours
         return slab[b] if slab.shape[0] == 1 else slab[b].copy()

@@ -204,6 +204,22 @@ class SimConfig:
         return NoiseModel(**kwargs)
 
 
+def _env_window_knots(default: int = 32) -> int:
+    """PULSER_AMD_WINDOW_KNOTS (knots per evaluation-time window): an integer >= 2; anything else gives the default and a
+    warning, like the native side's out-of-range RYD_* values (dev_common.hpp: dev_env_int)."""
+    env = os.environ.get("PULSER_AMD_WINDOW_KNOTS")
+    if env is None:
+        return default
+    try:
+        m = int(env)
+    except ValueError:
+        m = 0
+    if m < 2:
+        warnings.warn(f"PULSER_AMD_WINDOW_KNOTS={env!r} is not an integer >= 2; using {default}", stacklevel=2)
+        return default
+    return m
+
+
 def _as_inputs(sampled_seq: Any, register: Any, device: Any) -> SequenceInputs:
     if isinstance(sampled_seq, SequenceInputs):
         return sampled_seq
@@ -698,7 +714,7 @@ class QutipEmulator:
     # are the full sequence's polynomials, bit for bit).  Errors of a window do not travel beyond it.  12 - 16 atoms (measured,
     # one sequence, warm: 12 atoms 80 -> 35 ms, 14: 213 -> 80, 16: 253 -> 146); PULSER_AMD_NO_WINDOWS=1 keeps the sequential path.
     # (measured at 14 atoms, main solve + window solve: 16 knots 67.3 + 3.7 ms, 32: 61.3 + 4.7, 64: 58.6 + 6.8; the variable: tuning probe only)
-    _WINDOW_KNOTS = int(os.environ.get("PULSER_AMD_WINDOW_KNOTS", "32"))
+    _WINDOW_KNOTS = _env_window_knots()
     _WINDOW_TOL = 2e-11  # budget of a window solve = 500 x tol = 1e-8 (its error ends with the window)
 
     def _window_plan(self, tables: Any, mode: str, times: np.ndarray, kw: dict[str, Any]) -> Any:
@@ -756,9 +772,9 @@ class QutipEmulator:
             interaction=np.ascontiguousarray(inter), series_knots=[])
 
     def _solve_in_windows(self, eng: Any, tables: Any, state: Any, times: np.ndarray, kw: dict[str, Any],
-                          plan: Any) -> Any:
+                          plan: Any) -> tuple[Any, dict[str, Any]]:
         """The snapshots of ``eng.solve(state, times, store=True)`` - complex128[len(times) - 1, B, dim] - by anchors +
-        windows (see above).  ``state`` ends as the final state, like ``solve``."""
+        windows (see above), and the engine statistics of both solves.  ``state`` ends as the final state, like ``solve``."""
         from .engine import Engine
 
         torch = eng.torch
@@ -820,8 +836,7 @@ class QutipEmulator:
         merged["reserved"] = [stats["reserved"][0] + wstats["reserved"][0]] + list(stats["reserved"][1:])
         merged["windows"] = {"n_windows": B * J, "knots": m, "n_applications": wstats["n_applications"],
                              "n_launches": wstats["n_launches"], "estimate": wstats["reserved"][0]}
-        self._window_stats = merged
-        return out
+        return out, merged
 
     def _solve_batch(self, problems: list[dict[str, Any]], progress_bar: Any,
                      options: dict[str, Any], tables: Any = None,
@@ -871,30 +886,30 @@ class QutipEmulator:
             state = eng.new_state(init.reshape(1, -1))
             first = None if (on_device or raw) else state.cpu().numpy()  # (raw: nothing is wrapped, no host copy)
             first_dev = state.clone() if raw else None
-            self._window_stats = None
             if mode == "mcsolve":
                 snaps = eng.mc_solve(state, times, self._mc_seeds(n_batch, options), store=True,
                                      **self._engine_kwargs(options))
                 self.last_mc_jumps = eng.mc_jumps()
+                stats = eng.stats()
             else:
                 ekw = self._engine_kwargs(options)
                 plan = None if raw else self._window_plan(tables, mode, np.asarray(times, dtype=float), ekw)
                 if plan is not None:
-                    snaps = self._solve_in_windows(eng, tables, state, np.asarray(times, dtype=float), ekw, plan)
+                    snaps, stats = self._solve_in_windows(eng, tables, state, np.asarray(times, dtype=float), ekw, plan)
                 else:
                     snaps = eng.solve(state, times, store=True, **ekw)
+                    stats = eng.stats()
+            self.last_engine_stats = stats
             # large density matrices never cross PCIe as a whole: the results hold the device
             # tensors and reduce the diagonal (sampling weights, qutip_result.py:101-118) there
             if raw:
                 occ = eng.torch.stack([eng.occupations(first_dev)]
                                       + [eng.occupations(snaps[i]) for i in range(len(times) - 1)]).cpu().numpy()
-                self.last_engine_stats = eng.stats()
                 return first_dev, snaps, occ
             # ... and the other snapshots stay in HBM until somebody reads them (evaluation_times="Full", the reference's
             # default, stores 3 101 states per sequence: 813 MB at 14 atoms); results.states hands out LazyState objects
             store = None if on_device else SnapshotStore(snaps)
             del state
-            self.last_engine_stats = getattr(self, "_window_stats", None) or eng.stats()
         meas_errors = (
             {"epsilon": self.noise_model.p_false_pos, "epsilon_prime": self.noise_model.p_false_neg}
             if "SPAM" in self.noise_model.noise_types else None

@@ -237,3 +237,56 @@ def test_batched_cumulative_weights_are_bit_identical_to_the_per_state_path():
                     st = QState(arr[a, b]) if is_ket else QState(np.diag(arr[a, b]))
                     ref = np.cumsum(StateResult(qids, basis, st, matching)._weights())
                     assert np.array_equal(cum[a, b], ref), (basis, matching, is_ket, a, b)
+
+
+def test_staging_pool_hands_a_buffer_to_one_caller_at_a_time_and_keeps_two_idle():
+    """The replay's staging buffers (distributed.StagingPool): a checked-out buffer belongs to its caller until released,
+    released buffers are reused (pinned allocations cost more than the copies), at most two idle ones are kept."""
+    import threading
+
+    import torch
+
+    from pulser_amd.distributed import StagingPool
+
+    made = []
+
+    def alloc(shape, dtype):
+        made.append(torch.empty(shape, dtype=dtype))
+        return made[-1]
+
+    pool = StagingPool(alloc)
+    key = ((4, 3, 8), torch.complex128)
+    # two threads at once, one key: two buffers
+    barrier = threading.Barrier(2)
+    got = [None, None]
+
+    def take(k):
+        barrier.wait()
+        got[k] = pool.checkout(*key)
+
+    threads = [threading.Thread(target=take, args=(k,)) for k in range(2)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert got[0] is not got[1] and len(made) == 2
+    # released -> handed out again, to the next checkout of its key only
+    pool.release(got[0])
+    assert pool.checkout((4, 3, 9), torch.complex128) is not got[0] and len(made) == 3
+    again = pool.checkout(*key)
+    assert again is got[0] and len(made) == 3
+    # a checked-out buffer survives any number of checkouts of other keys; it is nobody else's meanwhile
+    for s in range(10):
+        pool.release(pool.checkout((s + 1, 2), torch.float64))
+    pool.release(got[1])
+    assert pool.checkout(*key) is got[1]
+    pool.release(again)
+    assert pool.checkout(*key) is again
+    # at most two idle buffers, the oldest dropped first
+    bufs = [pool.checkout((s + 20,), torch.float64) for s in range(3)]
+    for b in bufs:
+        pool.release(b)
+    assert len(pool._idle) == 2
+    n_made = len(made)
+    assert pool.checkout((20,), torch.float64) is not bufs[0] and len(made) == n_made + 1
+    assert pool.checkout((21,), torch.float64) is bufs[1] and pool.checkout((22,), torch.float64) is bufs[2]

@@ -1904,3 +1904,32 @@ def test_window_tables_are_cuts_of_the_full_sequence_tables():
                         assert np.array_equal(wt.pp[wid], pp[sid, anchors[j]: anchors[j] + m])
                 assert wt.desc[e, k]["drive_scale"] == desc[b, k]["drive_scale"]
     assert tables.batch == B and tables.pp is pp  # the full tables are untouched
+
+
+def test_window_knots_variable_falls_back_to_the_default_with_a_warning():
+    """PULSER_AMD_WINDOW_KNOTS (read once, at import): an integer >= 2 is taken as it is; anything else gives the default
+    32 and one warning naming the variable and the value (0 used to end in a ZeroDivisionError in _window_plan)."""
+    import subprocess
+    import sys
+
+    code = (
+        "import sys, warnings; sys.path.insert(0, sys.argv[1])\n"
+        "with warnings.catch_warnings(record=True) as w:\n"
+        "    warnings.simplefilter('always')\n"
+        "    from pulser_amd.simulation import QutipEmulator\n"
+        "msgs = [str(x.message) for x in w if 'PULSER_AMD_WINDOW_KNOTS' in str(x.message)]\n"
+        "print(QutipEmulator._WINDOW_KNOTS, len(msgs), msgs[0] if msgs else '', sep='|')\n"
+    )
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cases = {"0": 32, "-4": 32, "abc": 32, "16": 16}
+    procs = {v: subprocess.Popen([sys.executable, "-c", code, root], stdout=subprocess.PIPE, text=True,
+                                 env={**os.environ, "PULSER_AMD_WINDOW_KNOTS": v}) for v in cases}
+    for v, want in cases.items():
+        out, _ = procs[v].communicate(timeout=300)
+        assert procs[v].returncode == 0, v
+        knots, n_warn, msg = out.strip().split("|", 2)
+        assert int(knots) == want, (v, out)
+        if want == 16:
+            assert int(n_warn) == 0, (v, out)
+        else:
+            assert int(n_warn) == 1 and repr(v) in msg, (v, out)

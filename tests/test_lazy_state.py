@@ -202,3 +202,57 @@ def test_expect_takes_sparse_and_qobj_like_observables_and_evaluates_diagonal_on
         cr.expect(["sigma_z"])
     with pytest.raises(ValueError, match="Incompatible shape"):
         cr.expect([sp.eye(D // 2).tocsr()])
+
+
+
+def test_a_read_that_races_a_spill_reads_the_source_data(monkeypatch):
+    """A store read on one thread while another thread's new store spills it: every read is the source data, no read
+    raises.  A store is spilled once, so each iteration races a fresh one.  The reader yields the GIL at every line of
+    ``SnapshotStore.get`` (a line tracer on its thread), so that a spill can land between any two of them."""
+    import sys
+    import threading
+    import time
+
+    SnapshotStore.spill_all()
+    n, batch, dim = 8, 2, 4
+    rng = np.random.default_rng(2)
+    data = rng.normal(size=(n, batch, dim)) + 1j * rng.normal(size=(n, batch, dim))
+    monkeypatch.setenv("PULSER_AMD_SNAPSHOT_GB", str(1.5 * data.nbytes / 2**30))  # the budget holds one store
+    get_code = SnapshotStore.get.__code__
+
+    def yield_per_line(frame, event, arg):
+        if event == "line":
+            time.sleep(0)
+        return yield_per_line
+
+    errors: list[BaseException] = []
+    try:
+        for it in range(2000):
+            a = SnapshotStore(FakeTensor(data, []), bulk_after=10**9)  # every read a single-state device read
+            started, stop = threading.Event(), threading.Event()
+
+            def read(a=a, started=started, stop=stop, k=it):
+                sys.settrace(lambda frame, event, arg: yield_per_line if frame.f_code is get_code else None)
+                try:
+                    while not stop.is_set():
+                        i, b = k % n, k % batch
+                        if not np.array_equal(a.get(i, b), data[i, b]):
+                            raise AssertionError(f"state ({i}, {b}) read wrong")
+                        k += 1
+                        started.set()
+                except BaseException as exc:  # reported by the main thread
+                    errors.append(exc)
+                    started.set()
+
+            t = threading.Thread(target=read)
+            t.start()
+            started.wait()
+            SnapshotStore(FakeTensor(data.copy(), []))  # spills `a` while it is being read
+            assert a.device_tensor is None
+            stop.set()
+            t.join()
+            if errors:
+                break
+    finally:
+        SnapshotStore.spill_all()
+    assert not errors, f"iteration {it}: {errors[0]!r}"
