@@ -234,7 +234,7 @@ int ryd_set_collapse(ryd_handle* h, int32_t n_ops, const double* ops);
 int ryd_mc_solve(ryd_handle* h, void* state_dev, int32_t n_times, const double* times,
                  void* out_dev, const uint64_t* seeds, const ryd_opts* opts, void* stream);
 
-/* Number of collapses of every batch entry in the last ryd_mc_solve
+/* Number of collapses of every batch entry in the last ryd_mc_solve or ryd_general_mc_solve(_many)
  * (McResult.col_times lengths); synchronises `stream`.  counts: int32[batch] (host). */
 int ryd_mc_get_jumps(ryd_handle* h, int32_t* counts, void* stream);
 
@@ -253,9 +253,12 @@ typedef struct ryd_general_config {
   int32_t abi_version;
   int32_t batch;
   int32_t device;
-  int32_t reserved;
+  int32_t reserved;  /* flags: RYD_GENERAL_DENSITY, other bits 0 */
   int64_t dim;
 } ryd_general_config;
+
+/* ryd_general_config.reserved: the evolved vector is row-major vec(rho) (a Liouvillian handle) */
+#define RYD_GENERAL_DENSITY 1
 
 int ryd_general_create(const ryd_general_config* cfg, ryd_handle** out);
 int ryd_general_add_term(ryd_handle* h, int64_t nnz, const int32_t* row_ptr, const int32_t* col,
@@ -288,6 +291,31 @@ int ryd_general_add_diag_term(ryd_handle* h, const double* values, int32_t serie
 int ryd_general_solve_many(ryd_handle** hs, int32_t n, void* const* states_dev, int32_t n_times,
                            const double* times, void* const* outs_dev, const ryd_opts* opts,
                            void* stream);
+
+/* Replaces: qutip.mcsolve outside the tuned 2-level Ising case (simulation.py:705-735 with a multi-level basis,
+ * XY mode or a collapse operator whose sum C^dag C is not diagonal): the local collapse operators of
+ * Hamiltonian._build_collapse_operators (hamiltonian.py:97-124) on a general KET handle.  ops: complex128
+ * [n_ops][local_dim][local_dim] row-major, interleaved (host), placed on every atom; atom a is the base-local_dim
+ * digit of stride local_dim^(n_atoms-1-a), dim must be local_dim^n_atoms.  local_dim 2 .. 4, n_ops <= 16, any
+ * matrices (no diagonality requirement).  Appends -(1/2) sum_a sum_k C_k^dag C_k as one static local term, so
+ * ryd_solve integrates the no-jump evolution under H_eff; n_ops = 0 removes the term and the operators again.
+ * Not for handles created with RYD_GENERAL_DENSITY. */
+int ryd_general_set_collapse(ryd_handle* h, int32_t local_dim, int32_t n_atoms, int32_t n_ops, const double* ops);
+
+/* Replaces: qutip.mcsolve(H, psi0, tlist, c_ops, ntraj=batch) on a general handle with collapse operators:
+ * ryd_mc_solve's arguments and jump rule, unchanged (Philox4x32-10, key = seed, counter = jump index; threshold
+ * tested at the end of every CF4 step; candidates atom-major, operator-minor; stored and final states
+ * normalised).  One trajectory per batch entry, all of one Hamiltonian (the term tables are shared, states
+ * complex128[batch][dim]); seeds host uint64[batch].  ryd_mc_get_jumps reports the collapses. */
+int ryd_general_mc_solve(ryd_handle* h, void* state_dev, int32_t n_times, const double* times, void* out_dev,
+                         const uint64_t* seeds, const ryd_opts* opts, void* stream);
+
+/* ryd_general_solve_many for quantum-jump trajectories: problem b is one trajectory of handle hs[b] (batch 1,
+ * at most 4096 entries, collapse operators set) with seed seeds[b]; one launch, one workgroup per problem
+ * (the noise trajectories of a multi-level / XY run under qutip.mcsolve, simulation.py:903-915). */
+int ryd_general_mc_solve_many(ryd_handle** hs, int32_t n, void* const* states_dev, int32_t n_times,
+                              const double* times, void* const* outs_dev, const uint64_t* seeds,
+                              const ryd_opts* opts, void* stream);
 
 /* Test/bench hook (bit mask): 1 = disable the persistent small-N kernel, 2 =
  * disable the single-launch plan of small states (partner tiles read through

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "librydemu.so")
 RYD_ABI_VERSION = 1
 RYD_MAX_QUBITS = 30
 RYD_SESOLVE, RYD_MESOLVE = 0, 1
+RYD_GENERAL_DENSITY = 1  # ryd_general_config.reserved: the evolved vector is vec(rho)
 
 
 class RydError(RuntimeError):
@@ -114,6 +115,11 @@ SYMBOLS = {
                                             C.c_double]),
     "ryd_general_solve_many": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                          C.POINTER(RydOpts), C.c_void_p]),
+    "ryd_general_set_collapse": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ryd_general_mc_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(RydOpts), C.c_void_p]),
+    "ryd_general_mc_solve_many": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.POINTER(RydOpts), C.c_void_p]),
     "ryd_apply_generator": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
     "ryd_probabilities": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "ryd_occupations": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

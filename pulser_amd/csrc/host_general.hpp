@@ -13,6 +13,7 @@ extern "C" int ryd_general_create(const ryd_general_config* cfg, ryd_handle** ou
   HIPCHK(hipSetDevice(cfg->device));
   ryd_handle* h = new ryd_handle();
   h->general = true;
+  h->gen_density = (cfg->reserved & RYD_GENERAL_DENSITY) != 0;
   h->cfg.abi_version = cfg->abi_version;
   h->cfg.device = cfg->device;
   h->cfg.mode = RYD_SESOLVE;

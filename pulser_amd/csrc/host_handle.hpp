@@ -169,6 +169,13 @@ struct ryd_handle {
   unsigned long long* mc_seeds_dev = nullptr;
   cplx* mc_ops_dev = nullptr;
   int mc_slot = 0;
+  // quantum jumps on the general path (ryd_general_set_collapse): the decay is term gen_mc_term of gen_host
+  bool gen_density = false;  // created with RYD_GENERAL_DENSITY: the vector is vec(rho), no collapse operators
+  int gen_mc_term = -1;      // index of the -(1/2) sum C^dag C local term, -1: none
+  int gen_mc_d = 0, gen_mc_atoms = 0;  // local dimension / atoms the jump state was sized for
+  void* gen_mc_args_dev = nullptr;     // argument table of k_gen_traj_mc
+  size_t gen_mc_args_cap = 0;
+  std::vector<unsigned long long> gen_mc_seeds;  // of the current ryd_general_mc_solve
   ryd_stats stats{};
   // timing
   bool timing = false;
@@ -484,6 +491,7 @@ extern "C" void ryd_destroy(ryd_handle* h) {
   hipFree(h->gen_conj_dev);
   hipFree(h->gen_scale_dev);
   hipFree(h->mc_pool);
+  hipFree(h->gen_mc_args_dev);
   for (auto& t : h->gen_host) {
     hipFree((void*)t.dev.row_ptr);
     hipFree((void*)t.dev.col);

@@ -97,7 +97,10 @@ static unsigned mc_blocks(const ryd_handle* h) {
 }
 
 // Jump bookkeeping after one CF4 step of a Monte-Carlo solve (all on `st`).
+static int mc_after_step_general(ryd_handle* h, cplx* state, hipStream_t st);
+
 static int mc_after_step(ryd_handle* h, cplx* state, hipStream_t st) {
+  if (h->general) return mc_after_step_general(h, state, st);
   const unsigned nblk = mc_blocks(h);
   hipLaunchKernelGGL(k_mc_norm, dim3(nblk, h->B), dim3(256), 0, st, state, h->nb, h->mcs.norm2);
   hipLaunchKernelGGL(k_mc_reduced, dim3(nblk, h->B), dim3(256), 0, st, state, h->N, h->mcs, h->B, 0);
@@ -110,6 +113,12 @@ static int mc_after_step(ryd_handle* h, cplx* state, hipStream_t st) {
 
 // Snapshot of the state: a plain copy, or the normalised ket in a Monte-Carlo solve.
 static int snapshot_copy(ryd_handle* h, const cplx* state, cplx* dst, hipStream_t st) {
+  if (h->mc_active && h->general) {
+    hipLaunchKernelGGL(k_mcg_normalize, dim3(mc_blocks(h), h->B), dim3(256), 0, st, state, dst, (long long)h->dim,
+                       h->mcs.lastnorm);
+    HIPCHK(hipGetLastError());
+    return RYD_OK;
+  }
   if (h->mc_active) {
     hipLaunchKernelGGL(k_mc_normalize, dim3(mc_blocks(h), h->B), dim3(256), 0, st, state, dst, h->nb,
                        h->mcs.lastnorm);
@@ -433,8 +442,15 @@ static bool use_persistent(const ryd_handle* h) {
   return !h->general && h->cfg.mode == RYD_SESOLVE && h->N <= 13 && !h->force_generic;
 }
 
+static bool use_persistent_general_mc(const ryd_handle* h);
+static int run_persistent_general_mc(ryd_handle* h, cplx* state, const std::vector<StepDesc>& sched, cplx* snaps,
+                                     hipStream_t st);
+
 static int run_steps(ryd_handle* h, cplx* state, const std::vector<StepDesc>& sched, cplx* snaps,
                      hipStream_t st, const ryd_opts& o) {
+  if (h->general && h->mc_active)  // quantum jumps on the general path (host_mc_general.hpp)
+    return use_persistent_general_mc(h) ? run_persistent_general_mc(h, state, sched, snaps, st)
+                                        : run_generic(h, state, sched, snaps, st, o);
   if (krylov_selected(h, o)) return run_generic(h, state, sched, snaps, st, o);
   if (split_selected(h, o)) return run_split(h, state, sched, snaps, o, st);
   if (ket_path(h)) return run_ket(h, state, sched, snaps, o, st);
@@ -680,6 +696,7 @@ extern "C" int ryd_mc_solve(ryd_handle* h, void* state_dev, int32_t n_times, con
   int rc = check_ready(h);
   if (rc) return rc;
   if (!h->mc) return fail(RYD_ERR_STATE, "ryd_set_collapse has not been called");
+  if (h->general) return fail(RYD_ERR_INVALID, "general-path handle: use ryd_general_mc_solve");
   if (!state_dev || !seeds) return fail(RYD_ERR_INVALID, "null argument");
   HIPCHK(hipSetDevice(h->cfg.device));
   hipStream_t st = (hipStream_t)stream;

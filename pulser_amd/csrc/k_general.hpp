@@ -485,7 +485,20 @@ struct GenTrajArgs {
   double a1, a2;
 };
 
-__device__ __forceinline__ void gen_traj_body(const GenTrajArgs& A) {
+// quantum-jump trajectories on the persistent kernel (k_gen_traj_mc): one workgroup per trajectory
+struct GenMcTrajArgs {
+  GenTrajArgs g;      // g.state / g.snaps already offset to this trajectory
+  McState mc;         // the handle's jump state; this trajectory is entry b
+  long long snap_stride;  // entries between two snapshot slots (batch x dim)
+  unsigned long long seed;
+  int b, n_atoms;
+  int init;           // 1: start the trajectory here (threshold of jump 0, reference = initial norm)
+};
+#define GEN_MC_LDS ((MCG_TRAJ_SH + MCG_TRAJ_RHO) * sizeof(double))  // reduction scratch + reduced matrices
+
+// MCD = 0: the deterministic kernel (k_gen_traj, k_gen_traj_many); MCD = D: jump bookkeeping after every step
+template <int MCD>
+__device__ __forceinline__ void gen_traj_body(const GenTrajArgs& A, const GenMcTrajArgs* M = nullptr) {
   constexpr int NTT = 1024, R = 4;  // dim <= 4096
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cplx* ws0 = reinterpret_cast<cplx*>(smem);
@@ -502,6 +515,23 @@ __device__ __forceinline__ void gen_traj_body(const GenTrajArgs& A) {
     const int row = tid + j * NTT;
     psi[j] = row < dim ? A.state[row] : make_double2(0.0, 0.0);
     digits[j] = (A.d && row < dim) ? gen_pack_digits(row, A.d, A.n_dig) : 0ull;
+  }
+  McgTraj T{};
+  double* mc_sh = reinterpret_cast<double*>(tcB + MAX_GEN_TERMS);
+  double* mc_rho = mc_sh + MCG_TRAJ_SH;
+  if constexpr (MCD > 0) {
+    T.seed = M->seed;
+    if (M->init) {
+      double us;
+      mc_uniforms(T.seed, 0u, &T.target, &us);
+      T.count = 0;
+      T.n2 = T.ref = mcg_traj_norm(psi, dim, mc_sh);
+    } else {
+      T.target = M->mc.target[M->b];
+      T.ref = M->mc.refnorm[M->b];
+      T.n2 = M->mc.lastnorm[M->b];
+      T.count = M->mc.count[M->b];
+    }
   }
   for (int s = 0; s < A.n_steps; ++s) {
     const StepDesc sd = A.steps[s];
@@ -569,7 +599,17 @@ __device__ __forceinline__ void gen_traj_body(const GenTrajArgs& A) {
       for (int j = 0; j < R; ++j) psi[j] = w[j];
       __syncthreads();
     }
-    if (sd.snap >= 0 && A.snaps) {
+    if constexpr (MCD > 0) {
+      mcg_traj_step<MCD>(psi, digits, dim, M->n_atoms, M->mc.ops, M->mc.n_ops, ws0, mc_sh, mc_rho, T);
+      if (sd.snap >= 0 && A.snaps) {  // stored kets are normalised
+        const double ns = rsqrt(T.n2);
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+          const int row = tid + j * NTT;
+          if (row < dim) A.snaps[(size_t)sd.snap * M->snap_stride + row] = make_double2(ns * psi[j].x, ns * psi[j].y);
+        }
+      }
+    } else if (sd.snap >= 0 && A.snaps) {
 #pragma unroll
       for (int j = 0; j < R; ++j) {
         const int row = tid + j * NTT;
@@ -577,14 +617,29 @@ __device__ __forceinline__ void gen_traj_body(const GenTrajArgs& A) {
       }
     }
   }
+  if constexpr (MCD > 0) {  // the final ket normalised too; the bookkeeping continues from norm 1
+    const double ns = rsqrt(T.n2);
 #pragma unroll
-  for (int j = 0; j < R; ++j) {
-    const int row = tid + j * NTT;
-    if (row < dim) A.state[row] = psi[j];
+    for (int j = 0; j < R; ++j) {
+      const int row = tid + j * NTT;
+      if (row < dim) A.state[row] = make_double2(ns * psi[j].x, ns * psi[j].y);
+    }
+    if (tid == 0) {
+      M->mc.target[M->b] = T.target;
+      M->mc.refnorm[M->b] = T.ref / T.n2;
+      M->mc.lastnorm[M->b] = 1.0;
+      M->mc.count[M->b] = T.count;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const int row = tid + j * NTT;
+      if (row < dim) A.state[row] = psi[j];
+    }
   }
 }
 
-__global__ __launch_bounds__(1024) void k_gen_traj(const GenTrajArgs A) { gen_traj_body(A); }
+__global__ __launch_bounds__(1024) void k_gen_traj(const GenTrajArgs A) { gen_traj_body<0>(A); }
 
 // A batch of INDEPENDENT small general-path problems in one launch: workgroup b runs the whole schedule of
 // problem b from its own tables (the noise trajectories of a multi-level run, hamiltonian_data.py:913-931
@@ -592,5 +647,13 @@ __global__ __launch_bounds__(1024) void k_gen_traj(const GenTrajArgs A) { gen_tr
 // every trajectory brings its own terms - the systems are <= 4096 entries and their tables a few KB).
 __global__ __launch_bounds__(1024) void k_gen_traj_many(const GenTrajArgs* __restrict__ args) {
   const GenTrajArgs A = args[blockIdx.x];
-  gen_traj_body(A);
+  gen_traj_body<0>(A);
+}
+
+// Quantum-jump trajectories, workgroup i = trajectory i (of one batched handle or of n handles)
+template <int D>
+__global__ __launch_bounds__(1024) void k_gen_traj_mc(const GenMcTrajArgs* __restrict__ args) {
+  const GenMcTrajArgs* M = args + blockIdx.x;
+  const GenTrajArgs A = M->g;
+  gen_traj_body<D>(A, M);
 }

@@ -55,6 +55,7 @@ typedef double2 cplx;
 #include "k_apply14.hpp"
 #include "k_small.hpp"
 #include "k_mc.hpp"
+#include "k_mc_general.hpp"
 #include "k_traj.hpp"
 #include "k_traj_dm.hpp"
 #include "k_ket.hpp"
@@ -78,5 +79,6 @@ SPLITR_INSTANCES_14(SPLITR_EXTERN)
 #include "host_krylov.hpp"
 #include "host_split.hpp"
 #include "host_step.hpp"
+#include "host_mc_general.hpp"
 #include "host_observables.hpp"
 #include "host_replay.hpp"

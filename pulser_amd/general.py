@@ -100,8 +100,27 @@ def _embed(n: int, d: int, factors: Mapping[int, np.ndarray]) -> sp.csr_matrix:
 MATRIX_FREE_FROM = 4097  # evolved-vector length from which the matrix-free terms are the default
 
 
-def lower_general(problem: Mapping[str, Any], mesolve: bool, matrix_free: bool | None = None) -> GeneralTables:
-    """``matrix_free=None``: explicit CSR terms for the systems the one-launch kernel holds (<= 4096 entries:
+def local_collapse_ops(problem: Mapping[str, Any]) -> list[np.ndarray]:
+    """The local d x d collapse operators, one per entry of ``problem["collapse_ops"]`` and in that order
+    (hamiltonian.py:97-124 places each of them on every atom, operator-major)."""
+    ops = _local_ops(list(problem["eigenbasis"]))
+    paulis = problem.get("depolarizing_pauli_2ds", {})
+    out = []
+    for coeff, cop in problem.get("collapse_ops", []):
+        if isinstance(cop, str):
+            local = coeff * ops[cop] if cop in ops else sum(coeff * pc * ops[po] for pc, po in paulis[cop])
+        else:
+            local = coeff * np.asarray(cop, dtype=complex)
+        out.append(np.ascontiguousarray(local, dtype=np.complex128))
+    return out
+
+
+def lower_general(problem: Mapping[str, Any], mesolve: bool, matrix_free: bool | None = None,
+                  with_collapse: bool = False) -> Any:
+    """``with_collapse=True``: returns ``(tables, local_collapse_ops(problem))`` - the ket tables and the local
+    operators that ``GeneralEngine.set_collapse`` places on every atom (quantum-jump trajectories).
+
+    ``matrix_free=None``: explicit CSR terms for the systems the one-launch kernel holds (<= 4096 entries:
     every case of the reference's tests; precomputed indices beat the digit decode there), matrix-free terms
     above: the site-fused application measures 11 ms against 16 ms (CSR) and 34 ms (term by term, round 2)
     on a 40-ns solve at 19 683 amplitudes, and nothing of the operators' size is built or stored
@@ -112,11 +131,10 @@ def lower_general(problem: Mapping[str, Any], mesolve: bool, matrix_free: bool |
         # golden tests are run through them: RYD_GENERAL_MATRIX_FREE=1 pytest tests/test_gpu_emulator.py -m gpu)
         matrix_free = (d ** (2 * n if mesolve else n) >= MATRIX_FREE_FROM
                        or os.environ.get("RYD_GENERAL_MATRIX_FREE") == "1")
-    if matrix_free:
-        tables = _lower_matrix_free(problem, mesolve)
-        if tables is not None:
-            return tables
-    return _lower_csr(problem, mesolve)
+    tables = _lower_matrix_free(problem, mesolve) if matrix_free else None
+    if tables is None:
+        tables = _lower_csr(problem, mesolve)
+    return (tables, local_collapse_ops(problem)) if with_collapse else tables
 
 
 def _spline_pp(tknots: np.ndarray, series_knots: list) -> np.ndarray:

@@ -859,6 +859,8 @@ class QutipEmulator:
         if tables is None:
             mode = self._solver_mode(problems[0])
             if mode == "mcsolve" and not self._mc_fast_ok(problems[0]):
+                if options.get("general_jumps"):
+                    return self._solve_general_jumps(problems, options, mc_ntraj)
                 mode = "mesolve"
             if mode == "mcsolve":
                 if mc_ntraj is not None:
@@ -1074,11 +1076,100 @@ class QutipEmulator:
                                        meas_errors))
         return out
 
+    def _solve_general_jumps(self, problems: list[dict[str, Any]], options: dict[str, Any],
+                             mc_ntraj: int | None) -> list[CoherentResults]:
+        """``qutip.mcsolve`` for the problems the tuned jump kernels do not take (multi-level bases, XY mode,
+        a non-diagonal ``sum C^dag C``), as quantum-jump trajectories on the general path (``run(...,
+        general_jumps=True)``).  ``mc_ntraj=None``: one trajectory per problem (the noisy runs), kets as results;
+        else the deterministic run: ``mc_ntraj`` trajectories of ``problems[0]`` averaged into density matrices
+        like :meth:`_solve_mc_average`."""
+        from .engine import GeneralEngine
+        from .general import lower_general
+
+        times = self._eval_times_array
+        n = self._hamiltonian_data.n_qudits
+        init = np.asarray(self._initial_state)
+        if init.ndim == 2 and init.shape[0] == init.shape[1] and init.shape[0] > 1:
+            raise NotImplementedError(
+                "Quantum-jump trajectories need a ket as initial state; use "
+                "solver=Solver.MESOLVER with a density matrix.")
+        ket = init.reshape(-1)
+        kw = self._engine_kwargs(options, general=True)
+        meas_errors = (
+            {"epsilon": self.noise_model.p_false_pos, "epsilon_prime": self.noise_model.p_false_neg}
+            if "SPAM" in self.noise_model.noise_types else None
+        )
+        qids = tuple(self.samples_obj.qubit_ids)
+        t_unit = self._tot_duration * 1e-3
+
+        def wrap(states: list[np.ndarray]) -> CoherentResults:
+            results = [StateResult(qids, self._meas_basis, QState(st), self._meas_basis in self.basis_name,
+                                   evaluation_time=float(t / t_unit)) for st, t in zip(states, times)]
+            return CoherentResults(results, n, self.basis_name, times, self._meas_basis, meas_errors)
+
+        if mc_ntraj is not None:
+            tables, cops = lower_general(problems[0], mesolve=False, with_collapse=True)
+            D = tables.dim
+            if (len(times) * D * D * 16) > (16 << 30):
+                raise MemoryError(
+                    f"Averaged density matrices at {len(times)} evaluation times of a {n}-atom "
+                    "register do not fit; use fewer evaluation times.")
+            from .engine import outer_accumulate
+
+            chunk = int(max(1, min(mc_ntraj, 1024, (2 << 30) // max(1, D * 16 * len(times)))))
+            acc = None
+            done = 0
+            jumps = []
+            while done < mc_ntraj:
+                b = min(chunk, mc_ntraj - done)
+                with GeneralEngine(tables, batch=b) as eng:
+                    eng.set_collapse(cops)
+                    torch = eng.torch
+                    if acc is None:
+                        acc = torch.zeros((len(times), D, D), dtype=torch.complex128, device=eng.device)
+                    state = eng.new_state(ket)
+                    outer_accumulate(state, acc[0])
+                    snaps = eng.mc_solve(state, times, self._mc_seeds(b, options), **kw)
+                    for i in range(1, len(times)):
+                        outer_accumulate(snaps[i - 1], acc[i])
+                    jumps.append(eng.mc_jumps())
+                    self.last_engine_stats = eng.stats()
+                done += b
+            self.last_mc_jumps = np.concatenate(jumps)
+            return [wrap(list((acc / mc_ntraj).cpu().numpy()))]
+
+        lowered = [lower_general(prob, mesolve=False, with_collapse=True) for prob in problems]
+        seeds = self._mc_seeds(len(problems), options)
+        engines = [GeneralEngine(tables) for tables, _ in lowered]
+        try:
+            for eng, (_, cops) in zip(engines, lowered):
+                eng.set_collapse(cops)
+            states = [eng.new_state(ket) for eng in engines]
+            first = states[0].cpu().numpy()[0]
+            if len(engines) > 1 and all(eng.dim <= 4096 for eng in engines) and np.all(np.diff(times) > 0):
+                snaps = GeneralEngine.mc_solve_many(engines, states, times, seeds, **kw)
+            else:
+                snaps = [eng.mc_solve(st, times, seeds[i:i + 1], **kw)
+                         for i, (eng, st) in enumerate(zip(engines, states))]
+            self.last_mc_jumps = np.concatenate([eng.mc_jumps() for eng in engines])
+            self.last_engine_stats = engines[0].stats()
+            hosts = [s.cpu().numpy() for s in snaps]
+        finally:
+            for eng in engines:
+                eng.close()
+        return [wrap([first] + [h[i][0] for i in range(len(times) - 1)]) for h in hosts]
+
     def run(self, progress_bar: bool = False, print_progress: bool = False,
             **options: Any) -> SimulationResults:
         """simulation.py:800-883.  ``options`` accepts QuTiP's ``max_step`` (an
         upper bound on the step, us) plus the engine's ``tol``,
-        ``taylor_order``, ``magnus_tol``; QuTiP-only keys are ignored."""
+        ``taylor_order``, ``magnus_tol``; QuTiP-only keys are ignored.
+
+        ``general_jumps=True``: problems that take ``qutip.mcsolve`` but not the tuned 2-level jump kernels
+        (3- / 4-level bases, XY mode, collapse operators whose ``sum C^dag C`` is not diagonal) run as
+        quantum-jump trajectories on the general path - kets of d^N amplitudes, so registers beyond the
+        master equation's 2^26-entry Liouvillian (XY up to 26 atoms, 3 levels up to 16) - instead of the
+        default master-equation fallback.  Seeds follow ``seeds=`` exactly as on the 2-level path."""
         warnings.warn(
             "QutipEmulator is deprecated as of pulser 1.9. Please use QutipBackendV2 instead.",
             DeprecationWarning,
