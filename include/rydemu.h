@@ -205,6 +205,21 @@ int ryd_evolve(ryd_handle* h, void* state_dev, double t0, double t1,
 int ryd_solve(ryd_handle* h, void* state_dev, int32_t n_times, const double* times,
               void* out_dev, const ryd_opts* opts, void* stream);
 
+/* Per-entry snapshot map for batches whose entries want their states at different
+ * evaluation times (run_batch: a duration or parameter scan in one solve).  offsets:
+ * host int64[batch][n_slots], copied.  After the call, ryd_solve stores batch entry
+ * b's state at times[i] (i >= 1) to out_dev + offsets[b][i-1] * dim (offsets counted
+ * in kets) instead of slot i-1 of the dense layout; -1 leaves that state unstored,
+ * and out_dev memory no offset points at is never written.  Every path honours it:
+ * the persistent and register-resident kernels store through it, the multi-launch
+ * paths scatter each entry to its own offset.  n_slots must equal n_times - 1 of
+ * every later ryd_solve with out_dev (RYD_ERR_INVALID otherwise); n_slots = 0
+ * removes the map.  Only for two-level RYD_SESOLVE handles without collapse
+ * operators: any other handle, and ryd_mc_solve on a handle with a map, return
+ * RYD_ERR_UNSUPPORTED.  Synchronises the device (an earlier solve may still read
+ * the old map). */
+int ryd_set_snapshot_map(ryd_handle* h, int32_t n_slots, const int64_t* offsets);
+
 /* Replaces: the c_ops argument of qutip.mcsolve (simulation.py:705-727: with
  * collapse operators and stochastic noise Solver.DEFAULT picks qutip.mcsolve;
  * Solver.MCSOLVER forces it) - the local 2x2 collapse operators that

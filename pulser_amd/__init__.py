@@ -12,6 +12,7 @@ from .noise_model import NoiseModel
 from .results import (CoherentResults, NoisyResults, QState, SampledResult,
                       SimulationResults, StateResult)
 from .simulation import QutipEmulator, SimConfig, Solver
+from .batch import run_batch
 from . import backend
 from .backend import (EmulatorConfig, QutipBackend, QutipBackendV2, QutipConfig, Results, RydEmuBackend,
                       RydOperator, RydState, register_with_pulser)
@@ -23,4 +24,5 @@ __all__ = [
     "NoisyResults", "SimulationResults", "StateResult", "SampledResult", "QState",
     "SequenceInputs", "ChannelInput", "Slot", "HamiltonianData", "single_global_channel",
     "QutipBackendV2", "RydEmuBackend", "register_with_pulser", "QutipBackend", "EmulatorConfig", "QutipConfig", "RydState", "RydOperator", "Results", "backend",
+    "run_batch",
 ]

@@ -101,6 +101,7 @@ SYMBOLS = {
     "ryd_evolve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.POINTER(RydOpts), C.c_void_p]),
     "ryd_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(RydOpts), C.c_void_p]),
     "ryd_set_collapse": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "ryd_set_snapshot_map": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ryd_mc_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.POINTER(RydOpts), C.c_void_p]),
     "ryd_mc_get_jumps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -110,3 +110,13 @@ __device__ __forceinline__ double uniform_d(double v) {
   const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
   return __hiloint2double(hi, lo);
 }
+
+// Where batch entry b's snapshot of evaluation slot `slot` goes: the dense layout [slot][B][D] of ryd_solve, or with a
+// snapshot map (ryd_set_snapshot_map) map[b][slot] kets into `snaps` - null when the map leaves that state unstored.
+// The map is read with (uniform) loads only.
+__device__ __forceinline__ cplx* snap_dst(cplx* snaps, const long long* __restrict__ map, int map_slots, int slot, int B,
+                                          int b, size_t D) {
+  if (map == nullptr) return snaps + ((size_t)slot * B + b) * D;
+  const long long off = map[(size_t)b * map_slots + slot];
+  return off < 0 ? nullptr : snaps + (size_t)off * D;
+}

@@ -111,6 +111,10 @@ struct ryd_handle {
   bool sched_for_split = false;   // the schedule being built is run by the split-operator path (host_sched.hpp: dev probe)
   bool snaps_outside = false;     // test / bench hook: every evaluation time closes a run of k_split_reg (round 4) instead of a
                                   // snapshot taken inside the run
+  // ryd_set_snapshot_map: [B][snap_map_slots] ket offsets into ryd_solve's out_dev (device), or null (dense slots)
+  long long* snap_map_dev = nullptr;
+  int snap_map_slots = 0;
+  size_t snap_map_cap = 0;        // entries allocated at snap_map_dev
   bool split_s10 = false;         // scheme of the current split-operator solve (host_step.hpp decides per call)
   bool split_s6_only = false;     // test / bench hook: the 4th-order scheme with one-knot sub-steps (round 2)
   void* many_args_dev = nullptr;  // ryd_general_solve_many: argument table of the batched launch (first handle)
@@ -477,6 +481,7 @@ extern "C" void ryd_destroy(ryd_handle* h) {
   hipFree(h->desc_dev);
   hipFree(h->dterms_dev);
   hipFree(h->sched_dev);
+  hipFree(h->snap_map_dev);
   hipFree(h->many_args_dev);
   hipFree(h->ksched_dev);
   hipFree(h->kry_V);

@@ -223,6 +223,8 @@ static int run_ket(ryd_handle* h, cplx* state, const std::vector<StepDesc>& sche
   fill_ket_args(h, A);
   A.state = state;
   A.snaps = snaps;
+  A.snap_map = h->snap_map_dev;
+  A.snap_map_slots = h->snap_map_slots;
   A.steps = h->ksched_dev;
   A.n_steps = (int)ks.size();
   A.rows_log2 = 0;

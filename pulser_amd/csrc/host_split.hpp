@@ -88,6 +88,7 @@ static const double kSplitTolTotal = split_norm_two ? 8e-8 : 4e-8;
 static const double kRowsBudget = 5e-8;
 
 static int snapshot_copy(ryd_handle* h, const cplx* state, cplx* dst, hipStream_t st);
+static int snapshot_store(ryd_handle* h, const cplx* state, cplx* snaps, int slot, hipStream_t st);
 static int mc_after_step(ryd_handle* h, cplx* state, hipStream_t st);
 
 struct SubStep {
@@ -344,7 +345,7 @@ static int split_run(ryd_handle* h, cplx* buf, const SubStep* subs, int nsub, hi
       const bool cut = (marks && marks[s] >= 0) || s + 1 == nsub || (alt && (alt[s + 1] != 0) != (alt[s] != 0));
       if (!cut) continue;
       if ((rc = split_run(h, buf, subs + a, s - a + 1, st, alt ? alt[s] != 0 : s6_run))) return rc;
-      if (marks && marks[s] >= 0 && (rc = snapshot_copy(h, buf, snaps + (size_t)marks[s] * h->dim * h->B, st))) return rc;
+      if (marks && marks[s] >= 0 && (rc = snapshot_store(h, buf, snaps, marks[s], st))) return rc;
       a = s + 1;
     }
     return RYD_OK;
@@ -416,7 +417,12 @@ static int split_run(ryd_handle* h, cplx* buf, const SubStep* subs, int nsub, hi
     Ls.n = 0;
     if (any_inner) {
       A.snaps = snaps;
-      A.snap_stride = (long long)h->dim * B;
+      if (h->snap_map_dev) {
+        A.snap_map = h->snap_map_dev;
+        A.snap_map_slots = h->snap_map_slots;
+      } else {
+        A.snap_stride = (long long)h->dim * B;
+      }
       for (int s = 0; s + 1 < nsub; ++s)
         if (marks[s] >= 0) { R.snap[s] = marks[s]; Ls.sub[Ls.n] = s; Ls.slot[Ls.n] = marks[s]; ++Ls.n; }
     }
@@ -432,11 +438,12 @@ static int split_run(ryd_handle* h, cplx* buf, const SubStep* subs, int nsub, hi
     if (Ls.n > 0) {
       // the stored open states -> closed states, all of the run at once (the run itself was one workgroup per sequence)
       hipLaunchKernelGGL(k_split_snap_close, dim3((unsigned)((h->dim + 255) / 256), (unsigned)B, (unsigned)Ls.n), dim3(256), 0, st,
-                         snaps, A.snap_stride, h->e0_dev, A.e0_stride, h->split_coefs, (long long)B * N * 4, N, R, Ls);
+                         snaps, (long long)h->dim * B, h->e0_dev, A.e0_stride, h->split_coefs, (long long)B * N * 4, N, R, Ls,
+                         (const long long*)h->snap_map_dev, h->snap_map_slots);
       HIPCHK(hipGetLastError());
     }
     if (marks && marks[nsub - 1] >= 0 &&
-        (rc = snapshot_copy(h, buf, snaps + (size_t)marks[nsub - 1] * h->dim * B, st))) return rc;
+        (rc = snapshot_store(h, buf, snaps, marks[nsub - 1], st))) return rc;
     return RYD_OK;
   }
   if (loop14) {
@@ -981,7 +988,7 @@ static int run_split(ryd_handle* h, cplx* state, const std::vector<StepDesc>& sc
     int rcf;
     if (jumps && (rcf = mc_after_step(h, state, st))) return rcf;
     if (snaps && sched[k].snap >= 0)
-      return snapshot_copy(h, state, snaps + (size_t)sched[k].snap * h->dim * h->B, st);
+      return snapshot_store(h, state, snaps, sched[k].snap, st);
     return RYD_OK;
   };
   // Sub-steps across step boundaries (round 6).  The schedule cuts a smooth stretch - one polynomial over many knots - into

@@ -129,6 +129,17 @@ static int snapshot_copy(ryd_handle* h, const cplx* state, cplx* dst, hipStream_
   return RYD_OK;
 }
 
+// Snapshot of the state into evaluation slot `slot` of the caller's output: slot * B kets on (the dense layout), or with
+// a snapshot map (ryd_set_snapshot_map) each entry to its own offset (k_snap_scatter).
+static int snapshot_store(ryd_handle* h, const cplx* state, cplx* snaps, int slot, hipStream_t st) {
+  if (!h->snap_map_dev) return snapshot_copy(h, state, snaps + (size_t)slot * h->dim * h->B, st);
+  const unsigned blocks = (unsigned)std::min<size_t>((h->dim + 255) / 256, 1024);
+  hipLaunchKernelGGL(k_snap_scatter, dim3(blocks, h->B), dim3(256), 0, st, state, snaps, (const long long*)h->snap_map_dev,
+                     h->snap_map_slots, slot, (long long)h->dim);
+  HIPCHK(hipGetLastError());
+  return RYD_OK;
+}
+
 static int run_generic(ryd_handle* h, cplx* state, const std::vector<StepDesc>& sched,
                        cplx* snaps, hipStream_t st, const ryd_opts& o) {
   int rc;
@@ -155,7 +166,7 @@ static int run_generic(ryd_handle* h, cplx* state, const std::vector<StepDesc>& 
     }
     h->stats.n_steps++;
     if (h->mc_active && (rc = mc_after_step(h, state, st))) return rc;
-    if (d.snap >= 0 && snaps && (rc = snapshot_copy(h, state, snaps + (size_t)d.snap * h->dim * h->B, st)))
+    if (d.snap >= 0 && snaps && (rc = snapshot_store(h, state, snaps, d.snap, st)))
       return rc;
   }
   (void)bytes;
@@ -209,6 +220,8 @@ static int run_persistent(ryd_handle* h, cplx* state, const std::vector<StepDesc
   TrajArgs A;
   A.state = state;
   A.snaps = snaps;
+  A.snap_map = h->snap_map_dev;
+  A.snap_map_slots = h->snap_map_slots;
   A.pp = h->pp_dev;
   A.n_int = h->n_knots - 1;
   A.desc = h->desc_dev;
@@ -522,6 +535,9 @@ static int solve_impl(ryd_handle* h, void* state_dev, int32_t n_times, const dou
   if (!state_dev || !times || n_times < 2) return fail(RYD_ERR_INVALID, "need a state and >= 2 times");
   for (int i = 1; i < n_times; ++i)
     if (!(times[i] >= times[i - 1])) return fail(RYD_ERR_INVALID, "times must be non-decreasing");
+  if (h->snap_map_dev && out_dev && h->snap_map_slots != n_times - 1)
+    return fail(RYD_ERR_INVALID, "the snapshot map has %d slots, this solve %d evaluation times after the first",
+                h->snap_map_slots, n_times - 1);
   HIPCHK(hipSetDevice(h->cfg.device));
   if (!h->bounds_valid) { if (h->general) compute_bounds_general(h); else compute_bounds(h); }
   ryd_opts o;
@@ -607,12 +623,12 @@ static int solve_impl(ryd_handle* h, void* state_dev, int32_t n_times, const dou
         sched.back().snap = i - 1;
       } else {  // zero-length interval: the state is unchanged
         if (before == 0) {
-          if ((rc = snapshot_copy(h, state, snaps + (size_t)(i - 1) * h->dim * h->B, st))) return rc;
+          if ((rc = snapshot_store(h, state, snaps, i - 1, st))) return rc;
         } else {
           // duplicate time after at least one step: flush what we have, copy, continue
           if ((rc = run_steps(h, state, sched, snaps, st, o))) return rc;
           sched.clear();
-          if ((rc = snapshot_copy(h, state, snaps + (size_t)(i - 1) * h->dim * h->B, st))) return rc;
+          if ((rc = snapshot_store(h, state, snaps, i - 1, st))) return rc;
         }
       }
     }
@@ -622,6 +638,36 @@ static int solve_impl(ryd_handle* h, void* state_dev, int32_t n_times, const dou
                  times[n_times - 1], sched.size(),
                  std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count());
   return run_steps(h, state, sched, snaps, st, o);
+}
+
+extern "C" int ryd_set_snapshot_map(ryd_handle* h, int32_t n_slots, const int64_t* offsets) {
+  if (!h) return fail(RYD_ERR_INVALID, "null handle");
+  if (h->general || h->cfg.mode != RYD_SESOLVE || h->mc)
+    return fail(RYD_ERR_UNSUPPORTED, "a snapshot map needs a two-level sesolve handle without collapse operators");
+  if (n_slots < 0 || (n_slots > 0 && !offsets)) return fail(RYD_ERR_INVALID, "n_slots = %d and offsets %p", n_slots, offsets);
+  const size_t n = (size_t)n_slots * h->B;
+  for (size_t i = 0; i < n; ++i)
+    if (offsets[i] < -1) return fail(RYD_ERR_INVALID, "snapshot offset %lld of entry %zu is below -1", (long long)offsets[i], i / n_slots);
+  HIPCHK(hipSetDevice(h->cfg.device));
+  // an earlier solve may still read the old map
+  HIPCHK(hipDeviceSynchronize());
+  if (n_slots == 0) {
+    if (h->snap_map_dev) hipFree(h->snap_map_dev);
+    h->snap_map_dev = nullptr;
+    h->snap_map_cap = 0;
+    h->snap_map_slots = 0;
+    return RYD_OK;
+  }
+  if (h->snap_map_cap < n) {
+    if (h->snap_map_dev) hipFree(h->snap_map_dev);
+    h->snap_map_dev = nullptr;
+    h->snap_map_cap = 0;
+    HIPCHK(hipMalloc((void**)&h->snap_map_dev, n * sizeof(long long)));
+    h->snap_map_cap = n;
+  }
+  HIPCHK(hipMemcpy(h->snap_map_dev, offsets, n * sizeof(long long), hipMemcpyHostToDevice));
+  h->snap_map_slots = n_slots;
+  return RYD_OK;
 }
 
 extern "C" int ryd_evolve(ryd_handle* h, void* state_dev, double t0, double t1,
@@ -697,6 +743,7 @@ extern "C" int ryd_mc_solve(ryd_handle* h, void* state_dev, int32_t n_times, con
   if (rc) return rc;
   if (!h->mc) return fail(RYD_ERR_STATE, "ryd_set_collapse has not been called");
   if (h->general) return fail(RYD_ERR_INVALID, "general-path handle: use ryd_general_mc_solve");
+  if (h->snap_map_dev) return fail(RYD_ERR_UNSUPPORTED, "quantum-jump solves do not take a snapshot map");
   if (!state_dev || !seeds) return fail(RYD_ERR_INVALID, "null argument");
   HIPCHK(hipSetDevice(h->cfg.device));
   hipStream_t st = (hipStream_t)stream;

@@ -72,6 +72,8 @@ struct KetArgs {
   double fin_cs, fin_sn;    // global phase of this launch's steps, applied at the final store
   const double* ftab;       // [2][4][16] = exp(pre[k] n), exp(post[k] n)  (host-computed, device memory)
   double gauge_eps2;        // KET_GAUGE: |c|^2 below which a drive has no direction of its own
+  const long long* snap_map;  // snapshot map (ryd_set_snapshot_map): [B][snap_map_slots] ket offsets, or null
+  int snap_map_slots;
 };
 
 // MODE of k_ket:
@@ -615,8 +617,9 @@ __global__ __launch_bounds__(1 << LOGNT) void k_ket(const KetArgs A) {
         }
       }
     }
-    if (sd.snap >= 0 && A.snaps) {
-      cplx* o = A.snaps + ((size_t)sd.snap * gridDim.x + row) * D;
+    cplx* o = (sd.snap >= 0 && A.snaps) ? snap_dst(A.snaps, A.snap_map, A.snap_map_slots, sd.snap, (int)gridDim.x, (int)row, D)
+                                        : nullptr;
+    if (o) {
       int tid_sn = tid;
       asm volatile("" : "+v"(tid_sn));  // addresses recomputed here, not parked in scratch from the loads on
       if constexpr (GAUGE) {

@@ -316,3 +316,17 @@ __global__ __launch_bounds__(256) void k_selfcheck(const cplx* __restrict__ st, 
     if (bad != 0.0) atomicAdd(out + 2 * b + 1, bad);
   }
 }
+
+// Snapshot of a ket batch through a snapshot map (ryd_set_snapshot_map): entry b's state goes to snaps + map[b][slot]
+// kets, or nowhere when that offset is -1 - what the plain device-to-device copy of the dense layout becomes with a map
+// set (the multi-launch paths: tiled passes, Taylor, Lanczos, the split-operator passes).  grid (blocks, B).
+__global__ __launch_bounds__(256) void k_snap_scatter(const cplx* __restrict__ state, cplx* __restrict__ snaps,
+                                                      const long long* __restrict__ map, int map_slots, int slot,
+                                                      long long dim) {
+  const int b = blockIdx.y;
+  const long long off = map[(size_t)b * map_slots + slot];
+  if (off < 0) return;
+  const cplx* src = state + (size_t)b * dim;
+  cplx* dst = snaps + (size_t)off * dim;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < dim; i += (long long)gridDim.x * 256) dst[i] = src[i];
+}

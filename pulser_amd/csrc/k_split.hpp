@@ -863,11 +863,13 @@ __global__ __launch_bounds__(256) void k_split_diff(const cplx* __restrict__ x, 
 //   psi_closed[i] = cprod * exp(-i (wE E0[i] - sum_{k excited in i} Delta_k)) * psi_open[i]
 // with wE = a_{S+1} tau of the sub-step, Delta_k from the sub-step's closing record (k_split_coefs: record S nsub + 1 + s)
 // and cprod = the product of the cosines of the sub-step's last tan-form rotation (record S (s + 1) - 1 + n_pre, field 0; 1
-// when the run is not in tan form).  grid (2^N / 256, B, marked sub-steps).
+// when the run is not in tan form).  grid (2^N / 256, B, marked sub-steps).  map / map_slots: the snapshot map of the
+// handle, or null.
 __global__ __launch_bounds__(256) void k_split_snap_close(cplx* __restrict__ snaps, long long snap_stride,
                                                           const double* __restrict__ e0, long long e0_stride,
                                                           const double* __restrict__ coefs, long long stage_stride, int N,
-                                                          const SplitRun R, const SplitSnapList Ls) {
+                                                          const SplitRun R, const SplitSnapList Ls,
+                                                          const long long* __restrict__ map, int map_slots) {
   __shared__ double dl[SPLIT_NMAX];
   __shared__ double cp;
   const int b = blockIdx.y, q = blockIdx.z;
@@ -886,11 +888,18 @@ __global__ __launch_bounds__(256) void k_split_snap_close(cplx* __restrict__ sna
   const double wE = splitrun_a(R, s, splitrun_S(R, s)) * R.tau[s];
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= ((size_t)1 << N)) return;
+  // with a snapshot map (ryd_set_snapshot_map) exactly the kets k_split_reg<.., SNAP> stored there
+  size_t base = (size_t)Ls.slot[q] * snap_stride + ((size_t)b << N);
+  if (map) {
+    const long long off = map[(size_t)b * map_slots + Ls.slot[q]];
+    if (off < 0) return;
+    base = (size_t)off << N;
+  }
   double phi = wE * e0[(size_t)b * e0_stride + i];
   for (int k = 0; k < N; ++k) phi -= ((i >> k) & 1) ? 0.0 : dl[k];
   double sn, cs;
   sincos(phi, &sn, &cs);
-  cplx* v = snaps + (size_t)Ls.slot[q] * snap_stride + ((size_t)b << N) + i;
+  cplx* v = snaps + base + i;
   const cplx a = *v;
   const double c = cp;
   *v = make_double2(c * fma(a.x, cs, a.y * sn), c * fma(a.y, cs, -a.x * sn));

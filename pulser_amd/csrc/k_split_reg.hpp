@@ -786,13 +786,15 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
       stage(sg, std::false_type{});
       if (sg == snap_at) {
         const int slot = R.snap[snap_sub];
-        if (slot >= 0) {
+        const long long moff = (slot >= 0 && A.snap_map_slots > 0) ? A.snap_map[(size_t)b * A.snap_map_slots + slot] : 0;
+        if (slot >= 0 && moff >= 0) {
           // address = uniform base + the lane's word + a constant per register.  The lane's word is laundered through an
           // empty asm: loop-invariant otherwise, and the 32 hoisted 64-bit addresses cost 20 spilled vector registers
           // in every stage of the loop (measured: 10.6 instead of 9.4 us per stage)
           unsigned lw = odd ? L::index(true, tq, 0u) : L::index(false, tq, 0u);
           asm volatile("" : "+v"(lw));
-          cplx* __restrict__ sd = A.snaps + (size_t)slot * A.snap_stride + ((size_t)b << N);
+          cplx* __restrict__ sd = A.snap_map_slots > 0 ? A.snaps + ((size_t)moff << N)
+                                             : A.snaps + (size_t)slot * A.snap_stride + ((size_t)b << N);
           if (odd) {
             splitr_for<0, NA>([&](auto Rc) {
               constexpr int r = decltype(Rc)::value;

@@ -38,6 +38,9 @@ struct TrajArgs {
   McState mc;
   double mc_a, mc_b;  // real diagonal of G_eff: mc_a + mc_b * popc(index)
   int mc_jumps;       // 0: no-jump evolution under H_eff only
+  // snapshot map of the handle (ryd_set_snapshot_map): [B][map_slots] ket offsets into snaps, or null (dense slots)
+  const long long* snap_map;
+  int snap_map_slots;
 };
 
 // MODEL 0: per-atom complex drive coefficients (local addressing, noise).
@@ -429,8 +432,9 @@ __global__ __launch_bounds__(NTT) void k_traj(const TrajArgs A) {
         __syncthreads();  // partner reads of ws0 done before the next step rewrites it
       }
     }
-    if (sd.snap >= 0 && A.snaps && active) {
-      cplx* o = A.snaps + ((size_t)sd.snap * A.B + b) * D;
+    cplx* o = (sd.snap >= 0 && A.snaps && active) ? snap_dst(A.snaps, A.snap_map, A.snap_map_slots, sd.snap, A.B, b, D)
+                                                  : nullptr;
+    if (o) {
       const double ns = jumps ? rsqrt(mc_n2) : 1.0;  // stored kets are normalised
 #pragma unroll
       for (int j = 0; j < R; ++j) o[tid + j * NTT] = make_double2(ns * psi[j].x, ns * psi[j].y);

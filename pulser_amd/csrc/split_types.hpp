@@ -30,13 +30,20 @@ struct SplitArgs {
   int conj, use_pre, use_post;
   const double* ftab;
   int pend;  // k_split12<.., TAN>: a rotation precedes this pass's D (its cosine product is applied with D)
+  // k_split_reg<.., SNAP> with a snapshot map (ryd_set_snapshot_map): its slots per entry, and snap_map (below) holds the
+  // map; 0: the dense layout of snap_stride.  (Both sit where the layout had room: every other kernel taking SplitArgs
+  // sees the same argument offsets as without them.)
+  int snap_map_slots;
   // k_split_reg<.., SNAP>: evaluation-time snapshots taken INSIDE a closed run (round 5).  At the end of a sub-step s
   // with SplitRun.snap[s] >= 0 the kernel stores its registers - the OPEN state: the last D(a_{S+1}) of the sub-step is
   // fused into the next stage and the cosines of the last tan-form rotation ride on that stage too - to
   // snaps + snap[s] * snap_stride (+ the sequence's offset); k_split_snap_close then applies the closing phase and
   // the cosine product to every stored snapshot of the run at once, across the chip
   cplx* snaps;
-  long long snap_stride;
+  union {
+    long long snap_stride;      // snap_map_slots == 0
+    const long long* snap_map;  // snap_map_slots > 0: [B][snap_map_slots] ket offsets into snaps, -1 = not stored
+  };
   // k_split_reg (kets, not ROWS), round 6 - the step-size controller's check without copy / compare launches:
   //   dst      the final state is stored HERE instead of in place (the whole sub-step of a check runs from the state into
   //            the scratch buffer: no 2 x 16 B per amplitude copy before it);

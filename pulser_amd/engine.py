@@ -115,6 +115,7 @@ class Engine:
         )
         self._h = C.c_void_p()
         _lib.check(self.lib.ryd_create(C.byref(cfg), C.byref(self._h)))
+        self._snap_map: tuple[int, int] | None = None  # (slots, kets the map reaches) of set_snapshot_map
         self._upload()
 
     # -- lifetime ---------------------------------------------------------
@@ -289,22 +290,40 @@ class Engine:
         magnus_tol: float = 0.0,
         split_steps: int = 0,
         method: str = "auto",
+        out: Any = None,
     ) -> Any:
         """Advance ``state`` in place through ``times`` (us); with ``store``
         return complex128[len(times)-1, B, dim...] = the states at times[1:]
         (``result.states[1:]`` of the reference's solver call,
-        simulation.py:729-748)."""
+        simulation.py:729-748).  With a snapshot map (:meth:`set_snapshot_map`) the states go to their
+        mapped kets of a complex128[rows, dim] tensor instead - ``out`` if given (at least as many rows as the map
+        reaches; rows nothing maps to are left as they are), else a new one."""
         self._check_state(state)
         t = np.ascontiguousarray(times, dtype=np.float64)
         if t.ndim != 1 or len(t) < 2:
             raise ValueError("times must hold at least two values")
-        out = None
-        if store:
+        if store and self._snap_map is not None:
+            slots, rows = self._snap_map
+            if len(t) - 1 != slots:
+                raise ValueError(f"the snapshot map has {slots} slots, these times {len(t) - 1}")
+            if out is None:
+                out = self.torch.empty((rows, self.dim), dtype=self.torch.complex128, device=self.device)
+            elif (not isinstance(out, self.torch.Tensor) or out.dtype != self.torch.complex128 or not out.is_contiguous()
+                  or out.device != self.device or out.dim() != 2 or out.shape[1] != self.dim or out.shape[0] < rows):
+                raise ValueError(f"out must be a contiguous complex128 tensor [>= {rows}, {self.dim}] on {self.device}")
+        elif store and out is None:
             out = self.torch.empty(
                 (len(t) - 1,) + self.state_shape,
                 dtype=self.torch.complex128,
                 device=self.device,
             )
+        elif store:
+            if (not isinstance(out, self.torch.Tensor) or out.dtype != self.torch.complex128 or not out.is_contiguous()
+                    or out.device != self.device or tuple(out.shape) != (len(t) - 1,) + self.state_shape):
+                raise ValueError(f"out must be a contiguous complex128 tensor {(len(t) - 1,) + self.state_shape} "
+                                 f"on {self.device}")
+        else:
+            out = None
         opts = RydOpts(
             taylor_order=int(taylor_order),
             max_order=int(max_order),
@@ -327,6 +346,23 @@ class Engine:
         )
         self._split_budget_check(method, float(tol))
         return out
+
+    def set_snapshot_map(self, offsets: Any) -> None:
+        """``ryd_set_snapshot_map``: from now on :meth:`solve` stores batch entry b's state at ``times[i]`` to ket
+        ``offsets[b, i - 1]`` of its output (int64[batch, n_slots]; -1 = not stored), so that the entries of one solve
+        may ask for different evaluation times (:func:`pulser_amd.batch.solve_many`).  ``None`` removes the map.  Noiseless
+        two-level ket engines only."""
+        if offsets is None:
+            _lib.check(self.lib.ryd_set_snapshot_map(self._h, 0, None))
+            self._snap_map = None
+            return
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        if off.ndim != 2 or off.shape[0] != self.batch or off.shape[1] < 1:
+            raise ValueError(f"offsets must be int64[{self.batch}, n_slots >= 1], got shape {off.shape}")
+        if off.min() < -1:
+            raise ValueError("snapshot offsets are kets (>= 0) or -1")
+        _lib.check(self.lib.ryd_set_snapshot_map(self._h, int(off.shape[1]), off.ctypes.data))
+        self._snap_map = (int(off.shape[1]), int(off.max()) + 1)
 
     def mc_solve(
         self,

@@ -62,6 +62,7 @@ class DeviceTables:
     series_knots: list[np.ndarray]  # the knot arrays (for tests / bounds)
     collapse_local: np.ndarray | None = None  # complex128[n_ops][2][2] (Monte-Carlo solver)
     dterms: np.ndarray | None = None  # DTERM_DTYPE[n]: extra detuning terms (hf detuning noise)
+    t_end: np.ndarray | None = None  # lower_ragged: float64[batch], each entry's own end time (us)
 
 
 DESC_DTYPE = np.dtype(
@@ -266,4 +267,90 @@ def lower(problems: Sequence[Mapping[str, Any]]) -> DeviceTables:
         collapse_local=local_collapse_ops(
             p0.get("collapse_ops", []), p0["eigenbasis"], p0.get("depolarizing_pauli_2ds")
         ),
+    )
+
+
+def _rebase_cubic(p: np.ndarray, h: float) -> np.ndarray:
+    """The piece ``p`` (a3, a2, a1, a0 in powers of ``t - t_i``) re-expanded about ``t_i + h``: the same polynomial,
+    in the arithmetic ``ryd_set_series`` uses to test whether two pieces join (host_handle.hpp: join_ok)."""
+    a3, a2, a1, a0 = p
+    return np.array([a3, 3.0 * a3 * h + a2, 3.0 * a3 * h * h + 2.0 * a2 * h + a1, ((a3 * h + a2) * h + a1) * h + a0],
+                    dtype=np.complex128)
+
+
+def lower_ragged(problems: Sequence[Mapping[str, Any]]) -> DeviceTables:
+    """Lower problems of DIFFERENT durations (same register size, sampling rate and basis; registers may differ) to ONE
+    table set over the knots of the longest entry.
+
+    Every entry keeps its own spline pieces on its own knot intervals - those of ``lower([p])``, bit for bit, never
+    re-splined.  Its interval after its last knot, up to its end time ``d / 1000`` us, is integrated by every solo run
+    with the EXTRAPOLATED last cubic: the padded table carries that polynomial re-based to the new knot.  Beyond it the
+    entry's pieces are zero, so an entry past its own end evolves under its interaction diagonal only (nothing of it is
+    stored).  The kink at an entry's end stops multi-knot steps (the pieces no longer join there).  Each entry's knot
+    times must be a prefix of the longest entry's (always at sampling rate 1); otherwise ``ValueError``.
+    ``tables.t_end`` holds every entry's end time."""
+    if not problems:
+        raise ValueError("At least one problem is required.")
+    p0 = problems[0]
+    n = int(p0["n_qudits"])
+    rate = float(p0.get("sampling_rate", 1.0))
+    basis_name = p0["basis_name"]
+    for p in problems:
+        if int(p["n_qudits"]) != n or float(p.get("sampling_rate", 1.0)) != rate or p["basis_name"] != basis_name:
+            raise ValueError("All problems of a ragged batch must share N, sampling rate and basis.")
+        if p.get("collapse_ops"):
+            raise NotImplementedError("ragged batches are noiseless (sesolve) only")
+    durations = np.array([int(p["duration"]) for p in problems])
+    longest = int(np.argmax(durations))
+    tk = sampling_times(int(durations[longest]), rate)
+    n_pieces = len(tk) - 1
+    own: list[DeviceTables] = []
+    for p, d in zip(problems, durations):
+        tk_b = sampling_times(int(d), rate)
+        if len(tk_b) > len(tk) or not np.array_equal(tk_b, tk[: len(tk_b)]):
+            raise ValueError(f"the knot times of a {d} ns entry are not a prefix of those of the longest "
+                             f"({durations[longest]} ns) entry at sampling rate {rate}: solve them apart")
+        if len(tk_b) < 2:
+            raise ValueError(f"a {d} ns entry has fewer than two knots at sampling rate {rate}")
+        own.append(lower([p]))
+    pool: list[np.ndarray] = []
+    index: dict[bytes, int] = {}
+    desc = np.zeros((len(problems), n), dtype=DESC_DTYPE)
+    desc["drive_series"] = desc["det_series"] = desc["off_series"] = -1
+    mats = []
+    for b, t in enumerate(own):
+        m = t.pp.shape[1]  # the entry's own pieces
+        padded = np.zeros((t.pp.shape[0], n_pieces, 4), dtype=np.complex128)
+        padded[:, :m] = t.pp
+        if m < n_pieces:  # [t_{d-1}, t_end]: the extrapolated last cubic, re-based to knot d - 1
+            h = float(tk[m] - tk[m - 1])
+            for s in range(t.pp.shape[0]):
+                padded[s, m] = _rebase_cubic(t.pp[s, m - 1], h)
+        ids = []
+        for s in range(padded.shape[0]):
+            key = padded[s].tobytes()
+            if key not in index:
+                index[key] = len(pool)
+                pool.append(padded[s])
+            ids.append(index[key])
+        ids_arr = np.asarray(ids, dtype=np.int32)
+        for f in ("drive_series", "det_series", "off_series"):
+            sid = t.desc[0][f]
+            desc[b][f] = np.where(sid >= 0, ids_arr[np.maximum(sid, 0)], -1)
+        for f in ("drive_scale", "det_scale", "off_scale", "extra"):
+            desc[b][f] = t.desc[0][f]
+        mats.append(t.interaction[0])
+    # (a batch without any drive keeps lower()'s single all-zero series: every entry's pieces are zero)
+    pp = np.stack(pool) if pool else np.zeros((1, n_pieces, 4), dtype=np.complex128)
+    shared = all(np.array_equal(mats[0], u) for u in mats[1:])
+    return DeviceTables(
+        n_qubits=n,
+        batch=len(problems),
+        tknots=np.ascontiguousarray(tk, dtype=np.float64),
+        pp=np.ascontiguousarray(pp),
+        desc=desc,
+        interaction=np.ascontiguousarray(np.stack(mats[:1] if shared else mats)),
+        dissipator=None,
+        series_knots=[],
+        t_end=durations.astype(np.float64) / 1000.0,
     )
