@@ -1,7 +1,8 @@
 """-m gpu: the multi-GPU legs of bench.py executed BEFORE an 8-GPU node ever runs them: two ranks share the one
 GPU of the test box and reduce over gloo (``RYD_BENCH_BACKEND=gloo``; under RCCL only the backend of the
 collectives differs).  Checked: the JSON contract line, and that what the ranks compute does not depend on the
-number of ranks."""
+number of ranks.  These runs pass ``--full`` (roofline, parity, collective probe, cfg4's density-matrix pass); a plain
+run, the headline alone, is checked on its own."""
 from __future__ import annotations
 
 import json
@@ -28,10 +29,11 @@ def _free_port():
     return p
 
 
-def _bench(n_gpus, *flags, backend="gloo", torchrun=False):
+def _bench(n_gpus, *flags, backend="gloo", torchrun=False, full=True):
     env = dict(os.environ, RYD_BENCH_BACKEND=backend, RYD_BENCH_DETAIL=os.devnull)  # (keep the tree's bench_detail.json)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    args = ["bench.py", "--gpus", str(n_gpus), "--steps", "1", "--warmup", "0", "--no-cpu", "--no-extras", *flags]
+    args = ["bench.py", "--gpus", str(n_gpus), "--steps", "1", "--warmup", "0",
+            *(["--full", "--no-cpu", "--no-extras"] if full else []), *flags]
     if n_gpus == 1 and not torchrun:
         cmd = [sys.executable, *args]
     else:
@@ -145,4 +147,26 @@ def test_dump_outputs_writes_the_last_timed_step(tmp_path):
     assert err < 1e-7 and err == pytest.approx(det["parity_max_abs"], rel=1e-12)
     occ = np.load(dump / "occupations.npy")
     assert occ.dtype == np.float64 and occ.shape == (15,)
+    assert np.allclose(occ / 16, det["ensemble_mean_occupations"] + [det["ensemble_mean_norm"]], rtol=0, atol=1e-14)
+
+
+def test_plain_run_times_the_headline_alone(tmp_path):
+    """Without --full the benchmark sets up, warms up, times its steps, dumps and prints the line - no roofline pass, no
+    CPU baseline, no parity check, no legs, no secondary workloads.  What the timed steps computed is the same: the
+    dumped nominal sequence against the tight-oracle fixture, the occupation sums against the ensemble means."""
+    from pulser_amd import problem as P
+
+    dump = tmp_path / "out"
+    line, det = _bench(1, "--batch", "16", "--warmup", "1", "--dump-outputs", str(dump), full=False)
+    assert line["steps"] == 1 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["unit"] == "sim-us/s"
+    assert line["value"] == pytest.approx(16 * 3.1 / (line["ms_per_step"] * 1e-3), rel=1e-5)
+    assert line["roofline"] is None and line["cpu_baseline"] is None and "collective" not in line
+    assert "parity_max_abs" not in line["config"] and "single_sequence_sim_us_per_s" not in line["config"]
+    assert not {"also", "single_sequence", "lindblad", "parity_max_abs"} & set(det)
+    assert set(det["setup"]) == {"lowering_ms", "handle_and_upload_ms"}
+    psi = np.load(dump / "final_state.npy")
+    assert psi.dtype == np.float64 and psi.shape == (16, 2**14, 2)
+    _, fx = P.load_problem(os.path.join(ROOT, "tests", "golden", "ns_tri14_anneal.npz"))
+    assert np.max(np.abs(psi[0, :, 0] + 1j * psi[0, :, 1] - np.asarray(fx["oracle_states_tight"])[-1])) < 1e-7
+    occ = np.load(dump / "occupations.npy")
     assert np.allclose(occ / 16, det["ensemble_mean_occupations"] + [det["ensemble_mean_norm"]], rtol=0, atol=1e-14)
