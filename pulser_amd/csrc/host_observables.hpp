@@ -44,7 +44,7 @@ extern "C" int ryd_observe(ryd_handle* h, const void* state_dev, double t, int32
   const size_t D = (size_t)1 << N;
   if (what & (RYD_OBS_OCCUPATION | RYD_OBS_CORRELATION)) {
     hipLaunchKernelGGL(k_obs_pairs, dim3((unsigned)((D + 2047) / 2048), h->B), dim3(256), 0, st,
-                       (const cplx*)state_dev, N, dm ? 1 : 0, out_dev, stride);
+                       (const cplx*)state_dev, N, dm ? 1 : 0, what, out_dev, stride);
     HIPCHK(hipGetLastError());
     h->stats.n_launches++;
   }

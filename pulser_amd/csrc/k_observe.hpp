@@ -9,8 +9,9 @@
 
 // out[b][0..N-1] = <n_k>, out[b][N] = sum p, out[b][N+1 + k*N + l] = <n_k n_l>.
 // One block stages a chunk of probabilities in LDS; thread <-> (k, l) pair (several per thread when
-// N(N+1)/2 > blockDim); wave-uniform chunk index -> LDS broadcast reads.
-__global__ __launch_bounds__(256) void k_obs_pairs(const cplx* __restrict__ st, int N, int is_dm,
+// N(N+1)/2 > blockDim); wave-uniform chunk index -> LDS broadcast reads.  `what`: RYD_OBS_OCCUPATION and / or
+// RYD_OBS_CORRELATION - the slots of the one not asked for stay 0 (the norm is written with either).
+__global__ __launch_bounds__(256) void k_obs_pairs(const cplx* __restrict__ st, int N, int is_dm, int what,
                                                    double* __restrict__ out, int out_stride) {
   constexpr int CH = 2048;
   __shared__ double ps[CH];
@@ -40,13 +41,15 @@ __global__ __launch_bounds__(256) void k_obs_pairs(const cplx* __restrict__ st, 
     int k = 0, rem = pr;
     while (rem >= N - k) { rem -= N - k; ++k; }
     const int l = k + rem;
+    if (k != l && !(what & RYD_OBS_CORRELATION)) continue;
     const unsigned mk = 1u << (N - 1 - k), ml = 1u << (N - 1 - l);
     double s = 0.0;
     for (int i = 0; i < CH; ++i) {
       const unsigned g = (unsigned)(base + i);
       if (!(g & mk) && !(g & ml)) s += ps[i];  // n = 1 <=> bit 0 (local state 0 = r)
     }
-    if (k == l) atomicAdd(o + k, s);
+    if (k == l && (what & RYD_OBS_OCCUPATION)) atomicAdd(o + k, s);
+    if (!(what & RYD_OBS_CORRELATION)) continue;
     atomicAdd(o + N + 1 + k * N + l, s);
     if (k != l) atomicAdd(o + N + 1 + l * N + k, s);
   }

@@ -73,6 +73,8 @@ def test_backend_v2_observables_against_oracle(capfd):
         assert np.allclose(results.get_result("occupation", t), occ, atol=1e-7)
         corr = np.array(results.get_result("correlation_matrix", t))
         assert np.allclose(np.diag(corr), occ, atol=1e-7) and np.allclose(corr, corr.T)
+        nk = np.stack([1.0 - ((idx >> (n - 1 - k)) & 1) for k in range(n)], axis=1)
+        assert corr.shape == (n, n) and np.allclose(corr, (nk * p[:, None]).T @ nk, atol=1e-7)  # the oracle state's
         assert abs(results.get_result("fidelity", t) - abs(psi[0b010]) ** 2) < 1e-7
         h = ham.matrix(times[i]).toarray()
         e2 = np.vdot(h @ psi, h @ psi).real
