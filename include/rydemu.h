@@ -138,7 +138,10 @@ typedef struct ryd_stats {
   double norm_bound;      /* last spectral-norm bound (rad/us) */
   double reserved[4];     /* split-operator path: [0] accumulated local-error estimate of the last
                              solve (sum of local 2-norms: a bound on every amplitude error), [1] last
-                             measured local error, [2] its sub-step (us), [3] checkpoint restores */
+                             measured local error, [2] its sub-step (us), [3] checkpoint restores;
+                             general-path handles: [3] the kernel of the last generator application - 0 term by
+                             term (k_gen_apply, CSR terms included), 1 k_gen_apply_sites, 2 k_gen_apply_fused
+                             gathering from L2, 3 k_gen_apply_fused with the vector staged in LDS */
 } ryd_stats;
 
 /* Replaces: construction of Hamiltonian/QobjEvo objects
@@ -357,7 +360,8 @@ int ryd_general_mc_solve_many(ryd_handle** hs, int32_t n, void* const* states_de
  * 131072 = every evaluation time closes a run of k_split_reg (round 4) instead of a snapshot stored from the registers
  * inside the run (k_split_reg<.., SNAP> + k_split_snap_close),
  * 262144 = general path: the round-3 site kernel (k_gen_apply_sites) instead of the padded site tables of
- * k_gen_apply_fused (round 6).
+ * k_gen_apply_fused (round 6),
+ * 524288 = ryd_general_observe on density matrices: 5 columns of rho per chunk (the chunked path without a 1-GiB state).
  * Never needed for results. */
 int ryd_set_path(ryd_handle* h, int32_t force_generic);
 
@@ -400,6 +404,26 @@ int ryd_occupations(ryd_handle* h, const void* state_dev, double* out_dev,
 #define RYD_OBS_DENSITY 8
 int ryd_observe(ryd_handle* h, const void* state_dev, double t, int32_t what,
                 double* out_dev, void* stream);
+
+/* ryd_observe for a general-path handle - the d-level states of the 3-level "all" basis, leakage (d = 3 / 4) and XY
+ * mode, where the reference evaluates the same observables (default_observables.py:291-580 with H(t) of
+ * qutip_backend.py:259-264) through dense d^N operators.  `what`, the layout of out_dev (float64[batch][N*N + N + 3],
+ * N = n_atoms) and "entries that were not requested are 0, no host synchronisation" are ryd_observe's; the batch is
+ * ryd_general_config.batch.  n_k = |one><one|_k with one_digit in [0, local_dim); atom a is the base-local_dim digit of
+ * stride local_dim^(n_atoms-1-a) (the convention of ryd_general_set_collapse); local_dim 2 .. 4; dim must equal
+ * local_dim^n_atoms (its square on a RYD_GENERAL_DENSITY handle), else RYD_ERR_INVALID.
+ *   ket handle:      state_dev complex128[batch][dim]; energy moments from ONE generator application w = -iHx and one
+ *                    fused dot (<H> = -Im<x|w>, <H^2> = |w|^2) on whichever application kernel the handle uses.
+ *   ket handle with RYD_OBS_DENSITY: state_dev complex128[batch][dim][dim]; pair sums from the diagonal; Tr(H rho) and
+ *                    Tr(H^2 rho) from H applied to the COLUMNS of rho (staged through a tiled transpose into scratch the
+ *                    handle owns, at most 256 MiB: larger matrices go in column chunks), one batched launch per
+ *                    application and chunk, trace taken on the device.  rho is read as stored (not assumed Hermitian)
+ *                    and the real part of either trace is kept, as ryd_observe does.
+ *   RYD_GENERAL_DENSITY handle: state_dev is vec(rho); occupations and correlations from the diagonal;
+ *                    RYD_OBS_ENERGY returns RYD_ERR_UNSUPPORTED (the handle's generator is the Liouvillian, not H), as
+ *                    it does on a ket handle with collapse operators (H_eff). */
+int ryd_general_observe(ryd_handle* h, const void* state_dev, double t, int32_t what, int32_t local_dim,
+                        int32_t n_atoms, int32_t one_digit, double* out_dev, void* stream);
 
 /* Replaces: building rho0 = |psi><psi| inside qutip.mesolve for a ket input.
  * psi_dev complex128[batch][2^N] -> rho_dev complex128[batch][2^N][2^N]. */

@@ -370,36 +370,74 @@ class HamiltonianOperator:
     """The noiseless H(t) handed to observables (qutip_backend.py:259-264),
     matrix-free: ``apply_to`` runs the device generator kernel."""
 
-    def __init__(self, engine: Any, t_us: float, eigenstates: Sequence[str]) -> None:
+    def __init__(self, engine: Any, t_us: float, eigenstates: Sequence[str], energy_expected: bool = True) -> None:
         self._eng, self._t, self.eigenstates = engine, t_us, tuple(eigenstates)
-        self._observed: tuple[int, dict[str, Any]] | None = None
+        # general engines: whether the first pair request of a state also asks for the energy moments (False when
+        # no energy observable is configured: a density state then costs no generator application at all)
+        self._energy_expected = bool(energy_expected)
+        # id(state), pair sums by the digit counted, energy moments (None until asked for)
+        self._observed: tuple[int, dict[int, dict[str, Any]], dict[str, float] | None] | None = None
 
-    def observe(self, state: RydState) -> dict[str, Any] | None:
-        """Device-side values behind Occupation / CorrelationMatrix / Energy* for a ket of a
-        2-level register: ONE ``ryd_observe`` call per (state, evaluation time), shared by every
-        observable asking for it (kets: pair reduction + one generator application + one dot;
-        density matrices: pair reduction on the diagonal + one gather kernel for Tr(H rho), Tr(H^2 rho)).
-        None for multi-level registers: the host formulas are used then."""
-        if not hasattr(self._eng, "observe") or len(self.eigenstates) != 2:
+    def observe(self, state: RydState, one_state: str | None = None, *, pairs: bool = True) -> dict[str, Any] | None:
+        """Device-side values behind Occupation / CorrelationMatrix / Energy*: ``ryd_observe`` (2-level Ising engines)
+        or ``ryd_general_observe`` (multi-level bases, leakage, XY), shared by every observable of a (state,
+        evaluation time) - ONE call when the observables use one one-state (kets: pair reduction + one generator
+        application + one dot; density matrices: pair reduction on the diagonal + Tr(H rho), Tr(H^2 rho) on the
+        device).  ``"digit"`` of the result is the local state the pair sums count: always 0 on a 2-level Ising
+        engine (the caller complements), the index of ``one_state`` (or of the inferred one-state) on a general
+        engine.  ``pairs=False``: the caller reads ``energy`` / ``energy2`` only.  On a general engine a further
+        one-state of the same state costs one more pair reduction and no generator application, and the energies are
+        computed once, with the first pair request when an energy observable is configured, else when first asked for.
+        None where the engine cannot serve the request (no ``observe``, a density or batched engine, a dimension
+        mismatch, a one-state that cannot be resolved): the host formulas - and their error texts - are used then."""
+        eng = self._eng
+        if not hasattr(eng, "observe"):
             return None
-        if self._observed is not None and self._observed[0] == id(state):
-            return self._observed[1]
+        general = hasattr(eng, "local_dim")
+        if general:
+            if (eng.is_density or eng.batch != 1 or not 2 <= eng.local_dim <= 4
+                    or eng.local_dim != len(self.eigenstates) or eng.local_dim ** eng.n != eng.dim):
+                return None
+        elif len(self.eigenstates) != 2:
+            return None
+        if self._observed is None or self._observed[0] != id(state):
+            self._observed = (id(state), {}, None)
+        _, seen, energies = self._observed
+        digit: int | None = 0
+        if general:
+            try:
+                digit = list(self.eigenstates).index(one_state or state.infer_one_state())
+            except (RuntimeError, ValueError):  # nothing to infer (a 3-level state) or not an eigenstate
+                if pairs:
+                    return None
+                digit = None
+            if not pairs and seen:  # the energies do not depend on the digit: any pair result of this state serves
+                digit = next(iter(seen))
+        have_pairs = digit in seen
+        if have_pairs and (pairs or energies is not None):
+            return {**seen[digit], **(energies or {})}
         q = state.to_qobj()
-        if q.shape[0] != self._eng.dim:
+        if q.shape[0] != eng.dim:
             return None
         import torch
 
-        if q.isket:
-            x = torch.from_numpy(np.ascontiguousarray(np.asarray(q)[:, 0][None, :])).to(self._eng.device)
-            raw = self._eng.observe(x, self._t)
-        else:  # density matrix of a master-equation run, observed with the noiseless ket engine's H(t)
-            x = torch.from_numpy(np.ascontiguousarray(np.asarray(q)[None, :, :])).to(self._eng.device)
-            raw = self._eng.observe(x, self._t, density=True)
+        # ket, or the density matrix of a master-equation run observed with the noiseless ket engine's H(t)
+        host = np.asarray(q)[:, 0][None, :] if q.isket else np.asarray(q)[None, :, :]
+        x = torch.from_numpy(np.ascontiguousarray(host)).to(eng.device)
+        kw: dict[str, Any] = {} if q.isket else {"density": True}
+        want_energy = True
+        if general:
+            want_energy = energies is None and (not pairs or self._energy_expected)
+            # (the norm comes with the pair launch: an energy-only request keeps the occupations for it)
+            kw.update(one=0 if digit is None else digit, energy=want_energy, correlation=not have_pairs and digit is not None)
+        raw = eng.observe(x, self._t, **kw)
         n2 = float(raw["norm2"][0])
-        res = {"occupation": raw["occupation"][0] / n2, "correlation": raw["correlation"][0] / n2,
-               "energy": float(raw["energy"][0]) / n2, "energy2": float(raw["energy2"][0]) / n2}
-        self._observed = (id(state), res)
-        return res
+        if want_energy:
+            energies = {"energy": float(raw["energy"][0]) / n2, "energy2": float(raw["energy2"][0]) / n2}
+        if digit is not None and not have_pairs:
+            seen[digit] = {"occupation": raw["occupation"][0] / n2, "correlation": raw["correlation"][0] / n2, "digit": digit}
+        self._observed = (id(state), seen, energies)
+        return {**(seen[digit] if digit is not None else {}), **(energies or {})}
 
     def _h_on(self, arr: np.ndarray) -> np.ndarray:
         """H @ arr for a ket (D,1) or a matrix (D,D) of column vectors."""
@@ -645,11 +683,11 @@ class Occupation(Observable):
         return d
 
     def apply(self, *, state: RydState, hamiltonian: Any = None, **kw: Any) -> list:
-        dev = hamiltonian.observe(state) if hasattr(hamiltonian, "observe") else None
-        if dev is not None:  # device reduction; local state 0 is what the kernel counts
+        dev = hamiltonian.observe(state, self.one_state) if hasattr(hamiltonian, "observe") else None
+        if dev is not None:  # device reduction; a 2-level Ising engine counts local state 0, a general one `one` itself
             one = self.one_state or state.infer_one_state()
             occ0 = dev["occupation"]
-            return [float(v) for v in (occ0 if list(state.eigenstates).index(one) == 0 else 1.0 - occ0)]
+            return [float(v) for v in (occ0 if list(state.eigenstates).index(one) == dev["digit"] else 1.0 - occ0)]
         p = _probabilities(state)
         return [float(v) for v in p @ _one_mask(state, self.one_state)]
 
@@ -672,11 +710,11 @@ class CorrelationMatrix(Observable):
         return d
 
     def apply(self, *, state: RydState, hamiltonian: Any = None, **kw: Any) -> list[list]:
-        dev = hamiltonian.observe(state) if hasattr(hamiltonian, "observe") else None
+        dev = hamiltonian.observe(state, self.one_state) if hasattr(hamiltonian, "observe") else None
         if dev is not None:
             one = self.one_state or state.infer_one_state()
             c0, o0 = dev["correlation"], dev["occupation"]
-            if list(state.eigenstates).index(one) == 0:
+            if list(state.eigenstates).index(one) == dev["digit"]:
                 return c0.tolist()
             # <(1 - n_i)(1 - n_j)> = 1 - <n_i> - <n_j> + <n_i n_j>
             return (1.0 - o0[:, None] - o0[None, :] + c0).tolist()
@@ -689,7 +727,7 @@ class Energy(Observable):
     _base_tag = "energy"
 
     def apply(self, *, state: RydState, hamiltonian: Any, **kw: Any) -> float:
-        dev = hamiltonian.observe(state) if hasattr(hamiltonian, "observe") else None
+        dev = hamiltonian.observe(state, pairs=False) if hasattr(hamiltonian, "observe") else None
         if dev is not None:
             return dev["energy"]
         return float(np.real(hamiltonian.expect(state)))
@@ -701,7 +739,7 @@ class EnergySecondMoment(Observable):
     _base_tag = "energy_second_moment"
 
     def apply(self, *, state: RydState, hamiltonian: HamiltonianOperator, **kw: Any) -> float:
-        dev = hamiltonian.observe(state) if hasattr(hamiltonian, "observe") else None
+        dev = hamiltonian.observe(state, pairs=False) if hasattr(hamiltonian, "observe") else None
         if dev is not None:
             return dev["energy2"]
         applied = np.asarray(hamiltonian.apply_to(state).to_qobj())  # H|psi> or H rho H
@@ -715,7 +753,7 @@ class EnergyVariance(Observable):
     default_aggregation = "skip_warn"  # a variance is not averaged over trajectories (:503-504)
 
     def apply(self, *, state: RydState, hamiltonian: HamiltonianOperator, **kw: Any) -> float:
-        dev = hamiltonian.observe(state) if hasattr(hamiltonian, "observe") else None
+        dev = hamiltonian.observe(state, pairs=False) if hasattr(hamiltonian, "observe") else None
         if dev is not None:
             return dev["energy2"] - dev["energy"] ** 2
         second = EnergySecondMoment.apply(self, state=state, hamiltonian=hamiltonian)  # type: ignore[arg-type]
@@ -1537,11 +1575,13 @@ class QutipBackendV2:
                               else GeneralEngine(lower_general(noiseless, mesolve=False)))
             return holder[0]
 
+        wants_energy = any(isinstance(o, (Energy, EnergySecondMoment, EnergyVariance)) for o in config.observables)
+
         def fill(res: Results, coherent: Any) -> None:
             for r in coherent:
                 t = r.evaluation_time
                 state = RydState(r.state.unit(), eigenstates=eigenstates)
-                ham = HamiltonianOperator(noiseless_engine(), t * T / 1000, eigenstates)
+                ham = HamiltonianOperator(noiseless_engine(), t * T / 1000, eigenstates, energy_expected=wants_energy)
                 for cb in config.callbacks:
                     cb(config=config, t=float(t), state=state, hamiltonian=ham, result=res)
                 for obs in config.observables:

@@ -178,7 +178,7 @@ static int check_ready(const ryd_handle* h) {
 struct MixPoint;
 static int launch_eval_general(ryd_handle* h, const MixPoint& m, hipStream_t st);
 static int apply_general(ryd_handle* h, const MixPoint& m, const cplx* in, const cplx* base,
-                         cplx* out, double scale, hipStream_t st);
+                         cplx* out, double scale, hipStream_t st, int n_vec = 0);
 
 extern "C" int ryd_apply_generator(ryd_handle* h, const void* in_dev, void* out_dev, double t,
                                    void* stream) {

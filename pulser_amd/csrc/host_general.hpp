@@ -492,10 +492,12 @@ static int gen_build_sites(ryd_handle* h) {
   return RYD_OK;
 }
 
+// `n_vec` vectors of h->dim entries each (0: the handle's batch; ryd_general_observe applies H to columns of rho)
 static int apply_general(ryd_handle* h, const MixPoint& m, const cplx* in, const cplx* base,
-                         cplx* out, double scale, hipStream_t st) {
+                         cplx* out, double scale, hipStream_t st, int n_vec) {
   const int n = (int)h->gen_host.size();
   if (n == 0) return fail(RYD_ERR_STATE, "no terms: call ryd_general_add_term first");
+  const unsigned nv = n_vec > 0 ? (unsigned)n_vec : (unsigned)h->B;
   if (h->gen_fused_ok) {
     GenFusedArgs A;
     A.in = in;
@@ -515,12 +517,13 @@ static int apply_general(ryd_handle* h, const MixPoint& m, const cplx* in, const
     A.d = h->gen_d;
     A.n_dig = h->gen_ndig;
     A.scale = scale;
-    dim3 grid((unsigned)((h->dim + GEN_FUSED_ROWS - 1) / GEN_FUSED_ROWS), h->B);
+    dim3 grid((unsigned)((h->dim + GEN_FUSED_ROWS - 1) / GEN_FUSED_ROWS), nv);
     if (h->gen_fused_xlds) hipLaunchKernelGGL(k_gen_apply_fused<true>, grid, dim3(256), h->gen_fused_lds, st, A);
     else hipLaunchKernelGGL(k_gen_apply_fused<false>, grid, dim3(256), h->gen_fused_lds, st, A);
     HIPCHK(hipGetLastError());
     h->stats.n_launches++;
     h->stats.n_applications++;
+    h->stats.reserved[3] = h->gen_fused_xlds ? 3.0 : 2.0;
     return RYD_OK;
   }
   if (h->gen_sites_ok) {
@@ -539,11 +542,12 @@ static int apply_general(ryd_handle* h, const MixPoint& m, const cplx* in, const
     A.scale = scale;
     const size_t lds = (size_t)A.S.P * (sizeof(cplx) + sizeof(int)) + (size_t)((A.S.n_rs + 3) & ~3) * sizeof(int) +
                        (size_t)A.S.n_sites * sizeof(GenSite) + 16;
-    dim3 grid((unsigned)((h->dim + 255) / 256), h->B);
+    dim3 grid((unsigned)((h->dim + 255) / 256), nv);
     hipLaunchKernelGGL(k_gen_apply_sites, grid, dim3(256), lds, st, A);
     HIPCHK(hipGetLastError());
     h->stats.n_launches++;
     h->stats.n_applications++;
+    h->stats.reserved[3] = 1.0;
     return RYD_OK;
   }
   GenArgs A;
@@ -557,11 +561,12 @@ static int apply_general(ryd_handle* h, const MixPoint& m, const cplx* in, const
   A.d = h->gen_d;
   A.n_dig = h->gen_ndig;
   A.scale = scale;
-  dim3 grid((unsigned)((h->dim + 255) / 256), h->B);
+  dim3 grid((unsigned)((h->dim + 255) / 256), nv);
   hipLaunchKernelGGL(k_gen_apply, grid, dim3(256), 0, st, A);
   HIPCHK(hipGetLastError());
   h->stats.n_launches++;
   h->stats.n_applications++;
+  h->stats.reserved[3] = 0.0;
   (void)m;
   return RYD_OK;
 }

@@ -180,6 +180,10 @@ struct ryd_handle {
   void* gen_mc_args_dev = nullptr;     // argument table of k_gen_traj_mc
   size_t gen_mc_args_cap = 0;
   std::vector<unsigned long long> gen_mc_seeds;  // of the current ryd_general_mc_solve
+  // ryd_general_observe with RYD_OBS_DENSITY: the staged columns of rho and H applied to them (allocated on first use)
+  cplx* gen_obs_scratch = nullptr;
+  size_t gen_obs_scratch_bytes = 0;
+  bool gen_obs_small_chunks = false;  // test hook: 5 columns per chunk
   ryd_stats stats{};
   // timing
   bool timing = false;
@@ -497,6 +501,7 @@ extern "C" void ryd_destroy(ryd_handle* h) {
   hipFree(h->gen_scale_dev);
   hipFree(h->mc_pool);
   hipFree(h->gen_mc_args_dev);
+  hipFree(h->gen_obs_scratch);
   for (auto& t : h->gen_host) {
     hipFree((void*)t.dev.row_ptr);
     hipFree((void*)t.dev.col);

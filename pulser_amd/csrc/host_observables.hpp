@@ -5,6 +5,7 @@
 extern "C" int ryd_probabilities(ryd_handle* h, const void* state_dev, double* w_dev,
                                  int32_t reverse, void* stream) {
   if (!h || !state_dev || !w_dev) return fail(RYD_ERR_INVALID, "null argument");
+  if (h->general) return fail(RYD_ERR_INVALID, "not available on a general-path handle");
   HIPCHK(hipSetDevice(h->cfg.device));
   const size_t D = (size_t)1 << h->N;
   dim3 grid((unsigned)((D + 255) / 256), h->B);
@@ -17,6 +18,7 @@ extern "C" int ryd_probabilities(ryd_handle* h, const void* state_dev, double* w
 extern "C" int ryd_occupations(ryd_handle* h, const void* state_dev, double* out_dev,
                                void* stream) {
   if (!h || !state_dev || !out_dev) return fail(RYD_ERR_INVALID, "null argument");
+  if (h->general) return fail(RYD_ERR_INVALID, "not available on a general-path handle");
   HIPCHK(hipSetDevice(h->cfg.device));
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(hipMemsetAsync(out_dev, 0, (size_t)h->B * (h->N + 1) * sizeof(double), st));
@@ -80,8 +82,99 @@ extern "C" int ryd_observe(ryd_handle* h, const void* state_dev, double t, int32
   return RYD_OK;
 }
 
+// ryd_observe for a general-path handle (d-level registers): k_gen_observe.hpp
+static const size_t kGenObsScratchCap = (size_t)256 << 20;  // staged columns of rho + H applied to them
+
+extern "C" int ryd_general_observe(ryd_handle* h, const void* state_dev, double t, int32_t what, int32_t local_dim,
+                                   int32_t n_atoms, int32_t one_digit, double* out_dev, void* stream) {
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (!h->general) return fail(RYD_ERR_INVALID, "not a general-path handle: use ryd_observe");
+  if (!state_dev || !out_dev) return fail(RYD_ERR_INVALID, "null argument");
+  if (local_dim < 2 || local_dim > 4 || n_atoms < 1 || n_atoms > 26 || one_digit < 0 || one_digit >= local_dim)
+    return fail(RYD_ERR_INVALID, "observe: local_dim=%d n_atoms=%d one_digit=%d out of range", local_dim, n_atoms, one_digit);
+  size_t D = 1;
+  for (int i = 0; i < n_atoms; ++i) {
+    D *= (size_t)local_dim;
+    if (D > ((size_t)1 << 26)) return fail(RYD_ERR_INVALID, "observe: %d^%d exceeds 2^26", local_dim, n_atoms);
+  }
+  if (h->dim != (h->gen_density ? D * D : D))
+    return fail(RYD_ERR_INVALID, "observe: dim %lld is not %d^%d%s", (long long)h->dim, local_dim, n_atoms,
+                h->gen_density ? " squared" : "");
+  const bool dm = h->gen_density || (what & RYD_OBS_DENSITY) != 0;
+  if (dm && D > ((size_t)1 << 13)) return fail(RYD_ERR_INVALID, "observe: a %lld x %lld density matrix exceeds 2^26 entries", (long long)D, (long long)D);
+  if (what & RYD_OBS_ENERGY) {
+    if (h->gen_density)
+      return fail(RYD_ERR_UNSUPPORTED, "energy moments need a ket handle: this handle's generator is the Liouvillian");
+    if (h->gen_mc_term >= 0)
+      return fail(RYD_ERR_UNSUPPORTED, "energy moments need a handle without collapse operators (its generator is H_eff)");
+  }
+  HIPCHK(hipSetDevice(h->cfg.device));
+  hipStream_t st = (hipStream_t)stream;
+  const int N = n_atoms, B = h->B;
+  const int stride = N * N + N + 3, off = N * N + N + 1;
+  HIPCHK(hipMemsetAsync(out_dev, 0, (size_t)B * stride * sizeof(double), st));
+  if (what & (RYD_OBS_OCCUPATION | RYD_OBS_CORRELATION)) {
+    hipLaunchKernelGGL(k_gen_obs_pairs, dim3((unsigned)((D + 2047) / 2048), B), dim3(256), 0, st, (const cplx*)state_dev,
+                       (unsigned)D, N, local_dim, one_digit, dm ? 1 : 0, what, out_dev, stride);
+    HIPCHK(hipGetLastError());
+    h->stats.n_launches++;
+  }
+  if (!(what & RYD_OBS_ENERGY)) return RYD_OK;
+  MixPoint m;
+  m.idx1 = m.idx2 = find_interval(h, t);
+  m.u1 = m.u2 = t - h->tknots[m.idx1];
+  m.w1 = 1.0;
+  m.w2 = 0.0;
+  if ((rc = launch_eval_general(h, m, st))) return rc;
+  if (!dm) {
+    if ((rc = apply_general(h, m, (const cplx*)state_dev, nullptr, h->wA, 1.0, st))) return rc;
+    const unsigned nblk = (unsigned)std::min<size_t>(std::max<size_t>(D >> 10, 1), 1024);
+    hipLaunchKernelGGL(k_gen_obs_energy, dim3(nblk, B), dim3(256), 0, st, (const cplx*)state_dev, (const cplx*)h->wA, D,
+                       out_dev, stride, off);
+    HIPCHK(hipGetLastError());
+    h->stats.n_launches++;
+    return RYD_OK;
+  }
+  // density matrix on a ket handle: H on the columns of rho, nc columns of every batch entry per chunk
+  size_t nc = std::min<size_t>(D, kGenObsScratchCap / (2 * sizeof(cplx) * (size_t)B * D));
+  nc = std::min<size_t>(nc, 65535 / (size_t)B);  // (the batch axis of the application is blockIdx.y)
+  if (h->gen_obs_small_chunks) nc = std::min<size_t>(nc, 5);
+  if (nc < 1)  // (65535 / B >= 1: ryd_general_create caps the batch there)
+    return fail(RYD_ERR_UNSUPPORTED, "observe: one column of every batch entry (%d x %lld) exceeds the 256-MiB scratch cap", B, (long long)D);
+  const size_t half = nc * (size_t)B * D, bytes = 2 * half * sizeof(cplx);
+  if (bytes > h->gen_obs_scratch_bytes) {
+    if (h->gen_obs_scratch) HIPCHK(hipFree(h->gen_obs_scratch));
+    h->gen_obs_scratch = nullptr;
+    h->gen_obs_scratch_bytes = 0;
+    HIPCHK(hipMalloc((void**)&h->gen_obs_scratch, bytes));
+    h->gen_obs_scratch_bytes = bytes;
+  }
+  cplx* X = h->gen_obs_scratch;
+  cplx* W = X + half;
+  for (size_t c0 = 0; c0 < D; c0 += nc) {
+    const unsigned n = (unsigned)std::min<size_t>(nc, D - c0);
+    const int n_vec = (int)n * B;
+    const unsigned tblk = std::min<unsigned>((n + 255) / 256, 64);
+    hipLaunchKernelGGL(k_gen_obs_stage_cols, dim3((n + 31) / 32, (unsigned)((D + 31) / 32), B), dim3(256), 0, st,
+                       (const cplx*)state_dev, X, (unsigned)D, (unsigned)c0, n);
+    HIPCHK(hipGetLastError());
+    if ((rc = apply_general(h, m, X, nullptr, W, 1.0, st, n_vec))) return rc;   // W  = -i H X
+    hipLaunchKernelGGL(k_gen_obs_trace, dim3(tblk, B), dim3(256), 0, st, (const cplx*)W, (unsigned)D, (unsigned)c0, n, 0,
+                       out_dev, stride, off);
+    HIPCHK(hipGetLastError());
+    if ((rc = apply_general(h, m, W, nullptr, X, 1.0, st, n_vec))) return rc;   // W2 = -H^2 X
+    hipLaunchKernelGGL(k_gen_obs_trace, dim3(tblk, B), dim3(256), 0, st, (const cplx*)X, (unsigned)D, (unsigned)c0, n, 1,
+                       out_dev, stride, off);
+    HIPCHK(hipGetLastError());
+    h->stats.n_launches += 3;
+  }
+  return RYD_OK;
+}
+
 extern "C" int ryd_ket_to_dm(ryd_handle* h, const void* psi_dev, void* rho_dev, void* stream) {
   if (!h || !psi_dev || !rho_dev) return fail(RYD_ERR_INVALID, "null argument");
+  if (h->general) return fail(RYD_ERR_INVALID, "not available on a general-path handle");
   if (2 * h->N > RYD_MAX_QUBITS) return fail(RYD_ERR_INVALID, "2N exceeds %d", RYD_MAX_QUBITS);
   HIPCHK(hipSetDevice(h->cfg.device));
   const size_t DD = (size_t)1 << (2 * h->N);
@@ -123,6 +216,7 @@ static int outer_accumulate_impl(const void* psi_dev, int64_t B, int64_t D, cons
 extern "C" int ryd_outer_accumulate(ryd_handle* h, const void* psi_dev, const double* weights,
                                     void* acc_dev, void* stream) {
   if (!h || !psi_dev || !acc_dev) return fail(RYD_ERR_INVALID, "null argument");
+  if (h->general) return fail(RYD_ERR_INVALID, "not available on a general-path handle");
   if (2 * h->N > RYD_MAX_QUBITS) return fail(RYD_ERR_INVALID, "2N exceeds %d", RYD_MAX_QUBITS);
   HIPCHK(hipSetDevice(h->cfg.device));
   return outer_accumulate_impl(psi_dev, h->B, (int64_t)1 << h->N, weights, acc_dev, (hipStream_t)stream);

@@ -795,6 +795,7 @@ extern "C" int ryd_set_path(ryd_handle* h, int32_t force_generic) {
       if (ns != h->gen_no_sites) { h->gen_no_sites = ns; h->gen_sites_valid = false; }
       const bool nf = (force_generic & 262144) != 0;  // general path: k_gen_apply_sites (round 3) instead of the padded site tables
       if (nf != h->gen_no_fused) { h->gen_no_fused = nf; h->gen_sites_valid = false; }
+      h->gen_obs_small_chunks = (force_generic & 524288) != 0;  // ryd_general_observe, density states: 5 columns per chunk
     }
     {
       const bool small = (force_generic & 2048) != 0;

@@ -759,27 +759,74 @@ class GeneralEngine:
         return counts
 
     def apply_generator(self, x: Any, t: float) -> Any:
-        # the C side trusts the pointer: a mis-sized vector would read / write out of bounds
-        if (tuple(x.shape) != (1, self.dim) or x.dtype != self.torch.complex128
-                or not x.is_contiguous() or x.device != self.device):
-            raise ValueError(f"state must be a contiguous complex128 tensor of shape (1, {self.dim}) "
-                             f"on {self.device}, got {tuple(x.shape)} {x.dtype} on {x.device}")
-        out = self.torch.empty_like(x)
-        _lib.check(self.lib.ryd_apply_generator(self._h, x.data_ptr(), out.data_ptr(), float(t),
-                                                self._stream()))
-        return out
+        """``G(t) x`` for one vector ``(1, dim)`` or one per batch entry ``(batch, dim)``."""
+        # the C side trusts the pointer and launches the handle's batch: the output is sized for it
+        if tuple(x.shape) not in ((1, self.dim), (self.batch, self.dim)):
+            raise ValueError(f"state must be a contiguous complex128 tensor of shape (1, {self.dim}) or "
+                             f"({self.batch}, {self.dim}) on {self.device}, got {tuple(x.shape)} {x.dtype} on {x.device}")
+        rows = int(x.shape[0])
+        self._check_batch_state(x, rows)
+        if rows == self.batch:
+            out = self.torch.empty_like(x)
+            _lib.check(self.lib.ryd_apply_generator(self._h, x.data_ptr(), out.data_ptr(), float(t), self._stream()))
+            return out
+        # one vector on a batched handle: padded to the batch, the first row is the answer
+        xin = x.expand(self.batch, self.dim).contiguous()
+        out = self.torch.empty_like(xin)
+        _lib.check(self.lib.ryd_apply_generator(self._h, xin.data_ptr(), out.data_ptr(), float(t), self._stream()))
+        return out[:1].contiguous()
 
-    def set_path(self, force_multi_launch: bool, no_sites: bool = False, no_fused: bool = False) -> None:
+    def observe(self, state: Any, t: float, one: int = 0, occupation: bool = True, correlation: bool = True,
+                energy: bool = True, density: bool = False) -> dict[str, np.ndarray]:
+        """``ryd_general_observe``: occupations and correlation matrix of ``n_k = |one><one|_k`` (``one``: index of the
+        eigenstate, digit value) and the energy moments of every batch entry in one device call.  ``state``:
+        ``[batch, dim]`` (kets, or ``vec(rho)`` on a density engine); ``density``: this ket engine observes density
+        matrices ``[batch, dim, dim]`` with its Hamiltonian.  Returns the host arrays of :meth:`Engine.observe`:
+        ``norm2`` [B] (trace for density states), ``occupation`` [B, N], ``correlation`` [B, N, N], ``energy`` [B],
+        ``energy2`` [B] - NOT normalised (divide by ``norm2``)."""
+        one = int(one)
+        if not 0 <= one < self.local_dim:
+            raise ValueError(f"'one' must be a digit in [0, {self.local_dim}), got {one}")
+        if not 2 <= self.local_dim <= 4:
+            raise ValueError(f"observe takes local dimensions 2 - 4, got {self.local_dim}")
+        if density and self.is_density:
+            raise ValueError("density=True is for ket engines; a density engine observes vec(rho) as it is")
+        n = self.n
+        side = self.local_dim ** n
+        if side ** (2 if self.is_density else 1) != self.dim:
+            raise ValueError(f"dim {self.dim} is not {self.local_dim}^{n}" + (" squared" if self.is_density else ""))
+        if density:
+            want = (self.batch, self.dim, self.dim)
+            if (tuple(state.shape) != want or state.dtype != self.torch.complex128
+                    or not state.is_contiguous() or state.device != self.device):
+                raise ValueError(f"density matrix must be a contiguous complex128 tensor of shape {want} on "
+                                 f"{self.device}, got {tuple(state.shape)} {state.dtype} on {state.device}")
+        else:
+            self._check_batch_state(state, self.batch)
+        what = (1 if occupation else 0) | (2 if correlation else 0) | (4 if energy else 0) | (8 if density else 0)
+        out = self.torch.empty((self.batch, n * n + n + 3), dtype=self.torch.float64, device=self.device)
+        _lib.check(self.lib.ryd_general_observe(self._h, state.data_ptr(), float(t), what, self.local_dim, n, one,
+                                                out.data_ptr(), self._stream()))
+        o = out.cpu().numpy()
+        return {"occupation": o[:, :n], "norm2": o[:, n],
+                "correlation": o[:, n + 1:n + 1 + n * n].reshape(self.batch, n, n),
+                "energy": o[:, n * n + n + 1], "energy2": o[:, n * n + n + 2]}
+
+    def set_path(self, force_multi_launch: bool, no_sites: bool = False, no_fused: bool = False,
+                 observe_small_chunks: bool = False) -> None:
         """Test hook: one launch per Taylor stage instead of the persistent
         one-launch kernel used for vectors of at most 4096 entries; ``no_sites``: the term-by-term
         kernel instead of the site-fused application of matrix-free terms; ``no_fused``: the round-3 site kernel
-        (k_gen_apply_sites) instead of the padded site tables of k_gen_apply_fused."""
+        (k_gen_apply_sites) instead of the padded site tables of k_gen_apply_fused; ``observe_small_chunks``:
+        :meth:`observe` of density matrices takes 5 columns per chunk (the chunked path on a small state)."""
         _lib.check(self.lib.ryd_set_path(self._h, int(bool(force_multi_launch)) | (4096 if no_sites else 0)
-                                         | (262144 if no_fused else 0)))
+                                         | (262144 if no_fused else 0) | (524288 if observe_small_chunks else 0)))
 
     def stats(self) -> dict[str, Any]:
         s = RydStats()
         _lib.check(self.lib.ryd_get_stats(self._h, C.byref(s)))
         return {"n_applications": int(s.n_applications), "n_launches": int(s.n_launches),
                 "n_steps": int(s.n_steps), "passes": 1, "last_order": int(s.last_order),
-                "norm_bound": float(s.norm_bound)}
+                "norm_bound": float(s.norm_bound),
+                # kernel of the last generator application (ryd_stats.reserved[3] of a general handle)
+                "apply_path": ("terms", "sites", "fused", "fused_lds")[int(s.reserved[3])]}
