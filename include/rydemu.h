@@ -450,6 +450,17 @@ int ryd_outer_accumulate_dim(const void* psi_dev, int64_t batch, int64_t dim,
 int ryd_accumulate(const void* x_dev, double weight, int64_t count, void* acc_dev,
                    int32_t device, void* stream);
 
+/* Replaces: qutip.expect(obs, states) over the stored states (simresults.py:89-132) for an
+ * operator given by its non-zeros.  out[s] = sum_j conj(x_s[rows[j]]) vals[j] x_s[cols[j]]  (kets), or
+ * out[s] = sum_j vals[j] rho_s[cols[j]][rows[j]]  (density = 1, rho row-major dim x dim).
+ * State s starts at states_dev + s * stride complex128 elements (stride >= dim, or dim*dim).
+ * rows/cols int32[nnz] sorted by (row, col), vals complex128[nnz], out complex128[n_states];
+ * all device pointers.  out is overwritten (zeroed on the stream, then accumulated).
+ * nnz == 0 gives zeros; n_states == 0 launches nothing. */
+int ryd_expect_sparse(const void* states_dev, int64_t n_states, int64_t stride, int64_t dim,
+                      int32_t density, const int32_t* rows_dev, const int32_t* cols_dev,
+                      const void* vals_dev, int64_t nnz, void* out_dev, int32_t device, void* stream);
+
 int ryd_get_stats(const ryd_handle* h, ryd_stats* out);
 int ryd_reset_stats(ryd_handle* h);
 

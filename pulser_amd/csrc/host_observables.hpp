@@ -231,6 +231,38 @@ extern "C" int ryd_outer_accumulate_dim(const void* psi_dev, int64_t batch, int6
   return outer_accumulate_impl(psi_dev, batch, dim, weights, acc_dev, (hipStream_t)stream);
 }
 
+// out[s] = <x_s| O |x_s> (kets) or Tr(O rho_s) for O given by its sorted non-zeros: k_expect.hpp
+extern "C" int ryd_expect_sparse(const void* states_dev, int64_t n_states, int64_t stride, int64_t dim, int32_t density,
+                                 const int32_t* rows_dev, const int32_t* cols_dev, const void* vals_dev, int64_t nnz,
+                                 void* out_dev, int32_t device, void* stream) {
+  if (n_states < 0 || nnz < 0) return fail(RYD_ERR_INVALID, "expect: %lld states, %lld non-zeros", (long long)n_states, (long long)nnz);
+  if (nnz > INT32_MAX) return fail(RYD_ERR_INVALID, "expect: %lld non-zeros exceed 2^31 - 1", (long long)nnz);
+  if (dim < 1 || dim > INT32_MAX) return fail(RYD_ERR_INVALID, "expect: dim %lld outside [1, 2^31 - 1]", (long long)dim);
+  if (stride < (density ? dim * dim : dim))
+    return fail(RYD_ERR_INVALID, "expect: stride %lld is smaller than a %s of dim %lld", (long long)stride,
+                density ? "density matrix" : "ket", (long long)dim);
+  if (n_states == 0) return RYD_OK;
+  if (!out_dev) return fail(RYD_ERR_INVALID, "null argument");
+  if (nnz > 0 && (!states_dev || !rows_dev || !cols_dev || !vals_dev)) return fail(RYD_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipMemsetAsync(out_dev, 0, (size_t)n_states * sizeof(cplx), st));
+  if (nnz == 0) return RYD_OK;
+  const int64_t n_tiles = (n_states + kExpectTile - 1) / kExpectTile;
+  const dim3 grid((unsigned)((nnz + kExpectChunk - 1) / kExpectChunk), (unsigned)std::min<int64_t>(n_tiles, 65535));
+  if (density)
+    hipLaunchKernelGGL(k_expect_sparse<1>, grid, dim3(256), 0, st, (const cplx*)states_dev, (long long)n_states,
+                       (long long)stride, (long long)dim, rows_dev, cols_dev, (const cplx*)vals_dev, (long long)nnz,
+                       (double*)out_dev);
+  else
+    hipLaunchKernelGGL(k_expect_sparse<0>, grid, dim3(256), 0, st, (const cplx*)states_dev, (long long)n_states,
+                       (long long)stride, (long long)dim, rows_dev, cols_dev, (const cplx*)vals_dev, (long long)nnz,
+                       (double*)out_dev);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(RYD_ERR_HIP, "k_expect_sparse: %s", hipGetErrorString(e));
+  return RYD_OK;
+}
+
 extern "C" int ryd_accumulate(const void* x_dev, double weight, int64_t count, void* acc_dev,
                               int32_t device, void* stream) {
   if (!x_dev || !acc_dev || count <= 0) return fail(RYD_ERR_INVALID, "null argument or empty array");

@@ -71,6 +71,7 @@ SPLITR_INSTANCES_14(SPLITR_EXTERN)
 #endif
 #include "k_observe.hpp"
 #include "k_gen_observe.hpp"
+#include "k_expect.hpp"
 #include "k_general.hpp"
 #include "host_handle.hpp"
 #include "host_apply.hpp"

@@ -78,6 +78,54 @@ def accumulate(x: Any, acc: Any, weight: float = 1.0) -> None:
         torch.cuda.current_stream(x.device).cuda_stream))
 
 
+def expect_sparse(states: Any, operator: Any, *, density: bool = False) -> Any:
+    """``<x_s| O |x_s>`` for kets ``states`` complex128[S, D], or ``Tr(O rho_s)`` for density matrices
+    complex128[S, D, D] (``density=True``), on the device and for every state in one launch
+    (``ryd_expect_sparse``): ``qutip.expect`` of simresults.py:89-132 over the states of a run.  ``states`` is a
+    CUDA tensor whose inner dimensions are contiguous; dim 0 may be strided (``dev[:, b]`` of a ``[T, B, D]``
+    snapshot tensor).  ``operator`` is anything ``scipy.sparse`` accepts, D x D; only its stored non-zeros are
+    visited.  Returns a CUDA complex128 tensor [S]."""
+    import scipy.sparse as sp
+
+    torch = _torch()
+    if not (hasattr(states, "is_cuda") and states.is_cuda):
+        raise ValueError("states must be a CUDA tensor")
+    if states.dtype != torch.complex128:
+        raise TypeError("complex128 tensor expected")
+    if states.dim() != (3 if density else 2) or (density and states.shape[1] != states.shape[2]):
+        raise ValueError(f"shape {tuple(states.shape)} does not match {'[S, D, D]' if density else '[S, D]'}")
+    n_states, dim = int(states.shape[0]), int(states.shape[-1])
+    inner = (dim, 1) if density else (1,)
+    if dim < 1 or (n_states > 0 and tuple(states.stride()[1:]) != inner) or (n_states > 1 and states.stride(0) < dim ** len(inner)):
+        raise ValueError("the inner dimensions of states must be contiguous (dim 0 may be strided)")
+    m = sp.csr_matrix(operator) if not sp.issparse(operator) else operator.tocsr()
+    if m.shape[0] != m.shape[1]:
+        raise ValueError(f"square operator expected, got {tuple(m.shape)}")
+    if m.shape[0] != dim:
+        raise ValueError(f"operator of shape {tuple(m.shape)} does not match states of dimension {dim}")
+    if m.nnz >= 2**31:
+        raise ValueError(f"{m.nnz} non-zeros: at most 2^31 - 1")
+    m = m.astype(np.complex128)  # (a copy: the caller's matrix is not reordered)
+    m.sum_duplicates()
+    m.sort_indices()
+    nnz = int(m.nnz)
+    cols = np.ascontiguousarray(m.indices, dtype=np.int32)
+    rows = np.repeat(np.arange(dim, dtype=np.int32), np.diff(m.indptr))
+    if nnz and (len(rows) != nnz or cols.min() < 0 or cols.max() >= dim):
+        raise ValueError("operator indices outside [0, dim)")
+    out = torch.empty(n_states, dtype=torch.complex128, device=states.device)
+    if n_states == 0:
+        return out
+    idx = torch.from_numpy(np.concatenate([rows, cols])).to(states.device)
+    vals = torch.from_numpy(np.ascontiguousarray(m.data, dtype=np.complex128)).to(states.device)
+    stride = int(states.stride(0)) if n_states > 1 else dim ** len(inner)
+    _lib.check(_lib.load().ryd_expect_sparse(
+        states.data_ptr(), n_states, stride, dim, int(bool(density)), idx.data_ptr(), idx.data_ptr() + 4 * nnz,
+        vals.data_ptr(), nnz, out.data_ptr(), int(states.device.index or 0),
+        torch.cuda.current_stream(states.device).cuda_stream))
+    return out
+
+
 class Engine:
     """One ``ryd_handle``: a batch of B states of N atoms on one device.
 

@@ -699,11 +699,53 @@ class SimulationResults(collections.abc.Sequence):
                 out[i] = np.sum((a.real**2 + a.imag**2) * diag)
         return out
 
+    def _expect_sparse_on_device(self, states: Sequence[Any], m: Any) -> np.ndarray | None:
+        """<psi_t| m |psi_t> or Tr(m rho_t) of an observable the diagonal path does not serve, for the states that are still device snapshots
+        of one store, in one ``engine.expect_sparse`` call over the store's tensor ([times, sequences, D] kets or
+        [times, sequences, D, D] density matrices): only the values cross PCIe and nothing counts as a read of the store.
+        The other states (the initial state, states read earlier, another run's) take the host formula.  None when no state
+        is a snapshot on a GPU (spilled stores, host stand-in tensors): the caller's host loop serves those."""
+        import scipy.sparse as sp
+
+        live = [st for st in states if isinstance(st, LazyState) and st._store is not None and st._store.device_tensor is not None]
+        if not live:
+            return None
+        store, b = live[0]._store, live[0]._b
+        dev = store.device_tensor
+        D = int(m.shape[0])
+        ndim = getattr(dev, "dim", lambda: 0)()
+        if not getattr(dev, "is_cuda", False) or ndim not in (3, 4) or tuple(dev.shape[2:]) != (D,) * (ndim - 2):
+            return None
+        density = ndim == 4
+        from .engine import expect_sparse
+
+        on_dev = [isinstance(st, LazyState) and st._store is store and st._b == b for st in states]
+        idx = np.array([st._i for st, f in zip(states, on_dev) if f], dtype=np.int64)
+        if len(idx) == 1 or (len(idx) > 1 and np.all(np.diff(idx) == 1)):  # every time in order: a strided view, no copy
+            x = dev[int(idx[0]):int(idx[0]) + len(idx), b]
+        else:
+            import torch
+
+            x = dev[torch.from_numpy(idx).to(dev.device), b]
+        host = expect_sparse(x, m if sp.issparse(m) else sp.csr_matrix(m), density=density).cpu().numpy()
+        out = np.empty(len(states), dtype=complex)
+        k = 0
+        for i, (st, f) in enumerate(zip(states, on_dev)):
+            if f:
+                out[i] = host[k]
+                k += 1
+            else:
+                a = np.asarray(st)
+                out[i] = np.vdot(a, m @ a) if a.shape[1] == 1 and a.shape[0] > 1 else (m @ a).trace()
+        return out
+
     def expect(self, obs_list: Sequence[Any]) -> list:
         """simresults.py:89-132 (``qutip.expect`` of the observables over the stored states).  Observables: arrays,
         ``qutip.Qobj`` (by interface) or SciPy sparse matrices; sparse ones stay sparse, and DIAGONAL ones (occupations,
         projectors, correlation products - what a Rydberg user plots) are evaluated on the device from the run's
-        snapshots without reading a single state back."""
+        snapshots without reading a single state back.  Every other observable (sigma_x sums, exchange terms,
+        coherences, an energy; anything over density-matrix snapshots) goes through ``engine.expect_sparse``: one kernel
+        over the operator's non-zeros and all snapshots, again without a state leaving the device."""
         import scipy.sparse as sp
 
         if not isinstance(obs_list, (list, np.ndarray)):
@@ -737,6 +779,11 @@ class SimulationResults(collections.abc.Sequence):
             if is_diag and not self._use_pseudo_dens:
                 d = np.asarray(m.diagonal())
                 fast = self._expect_diagonal_on_device(states, d.real.copy() if herm else d.astype(complex))
+                if fast is not None:
+                    out.append(np.array(fast.real if herm else fast))
+                    continue
+            if not self._use_pseudo_dens:  # anything else, over kets or density matrices: the operator's non-zeros
+                fast = self._expect_sparse_on_device(states, m)
                 if fast is not None:
                     out.append(np.array(fast.real if herm else fast))
                     continue
