@@ -405,6 +405,33 @@ int ryd_occupations(ryd_handle* h, const void* state_dev, double* out_dev,
 int ryd_observe(ryd_handle* h, const void* state_dev, double t, int32_t what,
                 double* out_dev, void* stream);
 
+/* ryd_observe for every evaluation time of a run in one call: a memset and at most three launches for any n_times
+ * and any `what`, instead of one upload, five launches and one read-back per time.  Two-level Ising kets on a
+ * RYD_SESOLVE handle without collapse operators: a RYD_MESOLVE or Monte-Carlo handle, a RYD_OBS_DENSITY bit in `what`
+ * and a handle with extra detuning terms (ryd_set_detuning_terms) return RYD_ERR_UNSUPPORTED, a general-path handle
+ * RYD_ERR_INVALID - ryd_observe / ryd_general_observe serve those, one state at a time.
+ *   states_dev  state (i, b) starts at states_dev + i*stride_t + b*stride_b (strides in complex128 elements, every
+ *               offset 64-bit), is contiguous over its 2^N amplitudes and is observed at times[i].  A snapshot tensor
+ *               [n_times][n_batch][2^N] is stride_t = n_batch * 2^N, stride_b = 2^N; one sequence of a batched solve
+ *               is the same stride_t with n_batch = 1.  Strides below 2^N, null pointers, n_batch < 1: RYD_ERR_INVALID.
+ *   batch       the handle's batch is n_batch (entry b observed with problem b, as ryd_observe does) or 1 (the one
+ *               problem serves every b); anything else is RYD_ERR_INVALID.
+ *   times       host float64[n_times], in any order, repeats allowed; each resolves its knot interval as ryd_observe
+ *               does (a time on a knot belongs to the interval that starts there, the last knot to the last interval).
+ *   out_dev     float64[n_times][n_batch][N*N + N + 3], the layout of ryd_observe.  Entries that `what` does not ask
+ *               for are 0; the squared norm (slot N) is always written.
+ * <H> and <H^2> come from w = H x formed tile by tile inside the reduction (k_observe_many.hpp): no generator
+ * application, no work vector - ryd_stats.n_applications does not move, n_launches counts the launches made.  Agrees
+ * with ryd_observe within rounding (different summation order; atomics may move the last bits between calls).
+ * n_times = 0 returns RYD_OK and launches nothing.  Scratch for the coefficient table of all times is owned by the
+ * handle, grows on demand and is freed with it.  No host synchronisation except while that scratch grows.
+ * One stream per handle, as for ryd_observe (whose coefficient table and work vector are handle-owned too): a second
+ * call on ANOTHER stream may overwrite the table while the first call's kernels still read it - order such calls
+ * with an event or use the same stream. */
+int ryd_observe_many(ryd_handle* h, const void* states_dev, int32_t n_times, int32_t n_batch,
+                     int64_t stride_t, int64_t stride_b, const double* times, int32_t what,
+                     double* out_dev, void* stream);
+
 /* ryd_observe for a general-path handle - the d-level states of the 3-level "all" basis, leakage (d = 3 / 4) and XY
  * mode, where the reference evaluates the same observables (default_observables.py:291-580 with H(t) of
  * qutip_backend.py:259-264) through dense d^N operators.  `what`, the layout of out_dev (float64[batch][N*N + N + 3],

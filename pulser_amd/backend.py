@@ -29,7 +29,7 @@ from typing import Any, Callable, Mapping, Sequence
 import numpy as np
 
 from .noise_model import NoiseModel, has_stochastic_noise
-from .results import DeviceState, QState, multinomial
+from .results import DeviceState, LazyState, QState, multinomial
 from .simulation import QutipEmulator, Solver
 
 __all__ = [
@@ -240,6 +240,31 @@ class RydState:
     __hash__ = None  # type: ignore[assignment]
 
 
+class _DeferredRydState(RydState):
+    """The ``RydState`` of a device snapshot that nobody has read yet: ``RydState(lazy.unit(), ...)`` built on the
+    first access to its data.  ``eigenstates``, ``n_qudits``, ``qudit_dim`` and ``infer_one_state`` need no data, so
+    an evaluation time whose observables were all served by ``Engine.observe_many`` costs no device-to-host copy;
+    whoever does read the state (``StateResult``, ``BitStrings``, ``Fidelity``, ``Expectation``, a callback) gets
+    exactly the state the eager construction gives."""
+
+    def __init__(self, lazy: Any, *, eigenstates: Sequence[str]) -> None:
+        _validate_eigenstates(eigenstates)
+        self.eigenstates = tuple(eigenstates)
+        shape = tuple(int(v) for v in lazy.shape)
+        _validate_shape(shape, len(self.eigenstates))
+        self._n = int(round(math.log(shape[0], len(self.eigenstates))))
+        self._amplitudes = None
+        self._lazy = lazy
+        self._q: QState | None = None
+
+    @property
+    def _state(self) -> QState:  # type: ignore[override]
+        if self._q is None:
+            self._q = QState(np.asarray(self._lazy.unit()))
+            self._lazy = None
+        return self._q
+
+
 class RydOperator:
     """``QutipOperator`` (pulser_simulation/qutip_op.py:30-260) on a SciPy sparse
     matrix: the operator type of ``Expectation`` and of custom callbacks."""
@@ -438,6 +463,15 @@ class HamiltonianOperator:
             seen[digit] = {"occupation": raw["occupation"][0] / n2, "correlation": raw["correlation"][0] / n2, "digit": digit}
         self._observed = (id(state), seen, energies)
         return {**(seen[digit] if digit is not None else {}), **(energies or {})}
+
+    def seed(self, state: RydState, norm2: float, occupation: np.ndarray, correlation: np.ndarray,
+             energy: float | None = None, energy2: float | None = None) -> None:
+        """Hand over what ``Engine.observe_many`` computed for ``state`` at this time (not normalised, local state 0
+        counted): ``observe`` then returns it without a launch and without reading the state."""
+        n2 = float(norm2)
+        energies = None if energy is None else {"energy": float(energy) / n2, "energy2": float(energy2) / n2}
+        self._observed = (id(state), {0: {"occupation": occupation / n2, "correlation": correlation / n2, "digit": 0}},
+                          energies)
 
     def _h_on(self, arr: np.ndarray) -> np.ndarray:
         """H @ arr for a ket (D,1) or a matrix (D,D) of column vectors."""
@@ -1477,6 +1511,42 @@ def _adopt_pulser_config(config: Any) -> "QutipConfig":
         return mine.with_changes(callbacks=callbacks) if callbacks else mine
 
 
+def _observe_many_route(states: Sequence[Any], fires: Sequence[bool], engine: Any, n_eigenstates: int,
+                        min_times: int | None) -> tuple[Any, int, list[int]] | None:
+    """Which states of one ``CoherentResults`` a single ``Engine.observe_many`` call serves: (store, sequence of the
+    store, positions into ``states``), or None when the per-time path serves them all.  A position qualifies when a
+    built-in occupation / correlation / energy observable fires there (``fires``) and its state is an unread
+    ``LazyState`` ket of one ``SnapshotStore`` whose tensor ``[times, sequences, 2^N]`` is still on the GPU; the
+    engine must be the 2-level Ising ``Engine`` of one problem in sesolve mode without extra detuning terms, and at
+    least ``min_times`` positions must qualify (None: the path is off).  Everything else - the initial state, states
+    already read, spilled stores, density matrices, general engines - keeps the per-time path."""
+    if min_times is None or engine is None:
+        return None
+    if hasattr(engine, "local_dim") or not hasattr(engine, "observe_many") or n_eigenstates != 2:
+        return None
+    if getattr(engine, "batch", 0) != 1 or getattr(engine, "mode", None) != 0 or getattr(engine, "monte_carlo", False):
+        return None  # (mode 0 = RYD_SESOLVE)
+    dterms = getattr(getattr(engine, "tables", None), "dterms", None)
+    if dterms is not None and len(dterms):
+        return None
+    store, b, dev = None, 0, None
+    positions: list[int] = []
+    for pos, (st, f) in enumerate(zip(states, fires)):
+        if not f or not isinstance(st, LazyState) or st._store is None or not st.isket:
+            continue
+        if store is None:
+            dev = st._store.device_tensor
+            if (dev is None or not getattr(dev, "is_cuda", False) or getattr(dev, "dim", lambda: 0)() != 3
+                    or int(dev.shape[2]) != engine.dim):
+                continue
+            store, b = st._store, st._b
+        if st._store is store and st._b == b and st.shape[0] == engine.dim:
+            positions.append(pos)
+    if store is None or len(positions) < max(int(min_times), 1):
+        return None
+    return store, b, positions
+
+
 # ------------------------------------------------------------------- backend
 class QutipBackendV2:
     """qutip_backend.py:121-325 on the MI355X engine.  ``sequence`` is a
@@ -1486,6 +1556,10 @@ class QutipBackendV2:
     config_type: type  # = QutipConfig
     last_timing: dict[str, float] | None = None
     last_observable_engine_stats: dict[str, Any] | None = None
+    # From this many evaluation times on, the occupations, correlations and energy moments of a 2-level Ising ket run
+    # come from ONE Engine.observe_many call over the device snapshots instead of one upload, five launches and one
+    # read-back per time.  None switches that path off.  (Value: profiles/observe_many.md.)
+    observe_many_min_times: int | None = 128
 
     def __init__(self, sequence: Any, *, config: QutipConfig | None = None,
                  mimic_qpu: bool = False) -> None:
@@ -1536,7 +1610,8 @@ class QutipBackendV2:
         return options
 
     def run(self) -> Results:
-        return self._run_raw(self._sim_obj, self._config, dict(self._options))
+        return self._run_raw(self._sim_obj, self._config, dict(self._options),
+                             observe_many_min_times=self.observe_many_min_times)
 
     @staticmethod
     def run_from_sequence_samples(sequence_samples: Any, register: Any = None, device: Any = None,
@@ -1550,13 +1625,17 @@ class QutipBackendV2:
         return QutipBackendV2._run_raw(sim, cfg, QutipBackendV2._prepare(sim, cfg))
 
     @staticmethod
-    def _run_raw(sim: QutipEmulator, config: QutipConfig, options: dict[str, Any]) -> Results:
+    def _run_raw(sim: QutipEmulator, config: QutipConfig, options: dict[str, Any], *,
+                 observe_many_min_times: Any = "class") -> Results:
+        """``observe_many_min_times``: the threshold of the one-call observable path for this run (``run`` passes the
+        instance's, so a subclass or an instance may set its own); by default the class attribute."""
         from .engine import Engine, GeneralEngine
         from .general import lower_general
 
         eigenstates = sim._hamiltonian_data.eigenbasis
         qids = tuple(sim.samples_obj.qubit_ids)
         T = sim.total_duration_ns
+        min_times = QutipBackendV2.observe_many_min_times if observe_many_min_times == "class" else observe_many_min_times
         with_leakage = bool(getattr(config.noise_model, "with_leakage", False))
         holder: list[Any] = []  # the engine of the noiseless H(t), built on first use
 
@@ -1577,11 +1656,58 @@ class QutipBackendV2:
 
         wants_energy = any(isinstance(o, (Energy, EnergySecondMoment, EnergyVariance)) for o in config.observables)
 
+        pair_or_energy = (Occupation, CorrelationMatrix, Energy, EnergySecondMoment, EnergyVariance)
+        many_cache: dict[str, Any] = {}  # the observe_many result of the LAST store seen: shared by the sequences of
+        #                                  one batched solve and their repetitions, dropped with the next solve
+
+        def observed_many(rs: Sequence[Any]) -> dict[int, tuple[dict[str, np.ndarray], int, int]]:
+            """position in ``rs`` -> (observe_many result, its row, its column), {} on the per-time path."""
+            if min_times is None:
+                return {}
+            watchers = [o for o in config.observables if isinstance(o, pair_or_energy)]
+            if not watchers or not rs:
+                return {}
+            fires = [any(o._fires(config, float(r.evaluation_time), T) for o in watchers) for r in rs]
+            route = _observe_many_route([r.state for r in rs], fires, noiseless_engine(), len(eigenstates), min_times)
+            if route is None:
+                return {}
+            store, b, positions = route
+            idx = [rs[p].state._i for p in positions]
+            times_us = [rs[p].evaluation_time * T / 1000 for p in positions]
+            key = (tuple(idx), tuple(times_us))
+            if many_cache.get("store") is not store or many_cache.get("key") != key:
+                dev = store.device_tensor
+                if dev is None:  # spilled since the route was taken
+                    return {}
+                step = idx[1] - idx[0] if len(idx) > 1 else 1
+                if step > 0 and all(j - i == step for i, j in zip(idx, idx[1:])):
+                    x = dev[idx[0]:idx[-1] + 1:step]  # every time, or every k-th: a view, observed in place
+                else:
+                    import torch
+
+                    x = dev[torch.as_tensor(idx, dtype=torch.long, device=dev.device)]
+                many_cache.clear()
+                many_cache.update(store=store, key=key,
+                                  got=noiseless_engine().observe_many(x, times_us, energy=wants_energy))
+            got = many_cache["got"]
+            return {p: (got, row, b) for row, p in enumerate(positions)}
+
         def fill(res: Results, coherent: Any) -> None:
-            for r in coherent:
+            rs = list(coherent)
+            many = observed_many(rs)
+            for pos, r in enumerate(rs):
                 t = r.evaluation_time
-                state = RydState(r.state.unit(), eigenstates=eigenstates)
+                served = many.get(pos)
+                if many and isinstance(r.state, LazyState):
+                    # the one-call path is on: a snapshot crosses PCIe when an observable or a callback reads it
+                    state = _DeferredRydState(r.state, eigenstates=eigenstates)
+                else:
+                    state = RydState(r.state.unit(), eigenstates=eigenstates)
                 ham = HamiltonianOperator(noiseless_engine(), t * T / 1000, eigenstates, energy_expected=wants_energy)
+                if served is not None:
+                    got, row, b = served
+                    ham.seed(state, got["norm2"][row, b], got["occupation"][row, b], got["correlation"][row, b],
+                             *((got["energy"][row, b], got["energy2"][row, b]) if wants_energy else ()))
                 for cb in config.callbacks:
                     cb(config=config, t=float(t), state=state, hamiltonian=ham, result=res)
                 for obs in config.observables:
@@ -1666,6 +1792,7 @@ class QutipBackendV2:
             # diagnostics of the last run: wall-clock split and the launches of the noiseless-H engine
             QutipBackendV2.last_timing = timing
             QutipBackendV2.last_observable_engine_stats = holder[0].stats() if holder else None
+            many_cache.clear()
             for eng in holder:
                 eng.close()
 

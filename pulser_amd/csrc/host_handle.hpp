@@ -184,6 +184,13 @@ struct ryd_handle {
   cplx* gen_obs_scratch = nullptr;
   size_t gen_obs_scratch_bytes = 0;
   bool gen_obs_small_chunks = false;  // test hook: 5 columns per chunk
+  // ryd_observe_many: [n_times] ObsManyTime, then the coefficient table [n_times][B][N][4] (grown on demand), and the
+  // pinned host copy of the former with the event that says its last upload has been read
+  void* obs_many_dev = nullptr;
+  size_t obs_many_bytes = 0;
+  ObsManyTime* obs_many_pin = nullptr;
+  size_t obs_many_pin_cap = 0;  // entries
+  hipEvent_t obs_many_ev = nullptr;
   ryd_stats stats{};
   // timing
   bool timing = false;
@@ -502,6 +509,9 @@ extern "C" void ryd_destroy(ryd_handle* h) {
   hipFree(h->mc_pool);
   hipFree(h->gen_mc_args_dev);
   hipFree(h->gen_obs_scratch);
+  hipFree(h->obs_many_dev);
+  if (h->obs_many_pin) hipHostFree(h->obs_many_pin);
+  if (h->obs_many_ev) hipEventDestroy(h->obs_many_ev);
   for (auto& t : h->gen_host) {
     hipFree((void*)t.dev.row_ptr);
     hipFree((void*)t.dev.col);

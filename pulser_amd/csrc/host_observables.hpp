@@ -172,6 +172,89 @@ extern "C" int ryd_general_observe(ryd_handle* h, const void* state_dev, double 
   return RYD_OK;
 }
 
+// ryd_observe for every evaluation time of a run (two-level Ising kets): k_observe_many.hpp
+extern "C" int ryd_observe_many(ryd_handle* h, const void* states_dev, int32_t n_times, int32_t n_batch,
+                                int64_t stride_t, int64_t stride_b, const double* times, int32_t what,
+                                double* out_dev, void* stream) {
+  if (!h) return fail(RYD_ERR_INVALID, "null handle");
+  if (h->general) return fail(RYD_ERR_INVALID, "observe_many: not available on a general-path handle");
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (h->cfg.mode != RYD_SESOLVE || h->mc)
+    return fail(RYD_ERR_UNSUPPORTED, "observe_many: kets of a sesolve handle without collapse operators only");
+  if (what & RYD_OBS_DENSITY) return fail(RYD_ERR_UNSUPPORTED, "observe_many: RYD_OBS_DENSITY is not served (use ryd_observe)");
+  if (!h->dterms_host.empty())
+    return fail(RYD_ERR_UNSUPPORTED, "observe_many: handles with extra detuning terms are not served (use ryd_observe)");
+  const int N = h->N, B = h->B;
+  const int64_t D = (int64_t)1 << N;
+  if (n_times < 0 || n_batch < 1) return fail(RYD_ERR_INVALID, "observe_many: %d times, batch %d", n_times, n_batch);
+  if (B != n_batch && B != 1)
+    return fail(RYD_ERR_INVALID, "observe_many: a handle of batch %d cannot observe %d states per time (its batch or 1)", B, n_batch);
+  if (stride_t < D || stride_b < D)
+    return fail(RYD_ERR_INVALID, "observe_many: strides %lld / %lld are smaller than a ket of %lld amplitudes",
+                (long long)stride_t, (long long)stride_b, (long long)D);
+  if (n_times == 0) return RYD_OK;
+  if (!states_dev || !times || !out_dev) return fail(RYD_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  hipStream_t st = (hipStream_t)stream;
+  const int stride = N * N + N + 3;
+  const long long n_states = (long long)n_times * n_batch;
+  HIPCHK(hipMemsetAsync(out_dev, 0, (size_t)n_states * stride * sizeof(double), st));
+  const unsigned gy = (unsigned)std::min<long long>(n_states, 65535);
+  const bool pairs = (what & (RYD_OBS_OCCUPATION | RYD_OBS_CORRELATION)) || !(what & RYD_OBS_ENERGY);
+  if (pairs) {
+    hipLaunchKernelGGL(k_obs_pairs_many, dim3((unsigned)((D + 2047) / 2048), gy), dim3(256), 0, st,
+                       (const cplx*)states_dev, n_states, (int)n_batch, (long long)stride_t, (long long)stride_b, N, (int)what,
+                       out_dev, stride);
+    HIPCHK(hipGetLastError());
+    h->stats.n_launches++;
+  }
+  if (!(what & RYD_OBS_ENERGY)) return RYD_OK;
+  // the (interval, offset) of every time on the host, the table of every time in one launch
+  // (the scratch is the handle's: calls on one handle are ordered by using ONE stream, as with coefs_dev / wA of ryd_observe)
+  const size_t tm_bytes = ((size_t)n_times * sizeof(ObsManyTime) + 255) & ~(size_t)255;
+  const size_t need = tm_bytes + (size_t)n_times * B * N * 4 * sizeof(double);
+  if (need > h->obs_many_bytes) {
+    HIPCHK(hipStreamSynchronize(st));  // (an earlier call on this stream may still read the old scratch)
+    if (h->obs_many_dev) HIPCHK(hipFree(h->obs_many_dev));
+    h->obs_many_dev = nullptr;
+    h->obs_many_bytes = 0;
+    HIPCHK(hipMalloc(&h->obs_many_dev, need));
+    h->obs_many_bytes = need;
+  }
+  if (!h->obs_many_ev) HIPCHK(hipEventCreateWithFlags(&h->obs_many_ev, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(h->obs_many_ev));  // the last upload has left the pinned buffer
+  if ((size_t)n_times > h->obs_many_pin_cap) {
+    if (h->obs_many_pin) HIPCHK(hipHostFree(h->obs_many_pin));
+    h->obs_many_pin = nullptr;
+    h->obs_many_pin_cap = 0;
+    HIPCHK(hipHostMalloc((void**)&h->obs_many_pin, (size_t)n_times * sizeof(ObsManyTime), hipHostMallocDefault));
+    h->obs_many_pin_cap = (size_t)n_times;
+  }
+  for (int i = 0; i < n_times; ++i) {
+    const int idx = find_interval(h, times[i]);
+    h->obs_many_pin[i].idx = idx;
+    h->obs_many_pin[i].u = times[i] - h->tknots[idx];
+    h->obs_many_pin[i].pad = 0;
+  }
+  ObsManyTime* tm_dev = (ObsManyTime*)h->obs_many_dev;
+  double* table = (double*)((char*)h->obs_many_dev + tm_bytes);
+  HIPCHK(hipMemcpyAsync(tm_dev, h->obs_many_pin, (size_t)n_times * sizeof(ObsManyTime), hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(h->obs_many_ev, st));
+  const long long total = (long long)n_times * B * N;
+  hipLaunchKernelGGL(k_eval_coefs_many, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const cplx*)h->pp_dev,
+                     h->n_knots - 1, (const ryd_qdesc*)h->desc_dev, (const ObsManyTime*)tm_dev, B * N, total, table);
+  HIPCHK(hipGetLastError());
+  h->stats.n_launches++;
+  const unsigned gx = (unsigned)std::max<int64_t>(D >> kObsManyTB, 1);
+  hipLaunchKernelGGL(k_obs_energy_many, dim3(gx, gy), dim3(256), 0, st, (const cplx*)states_dev, n_states, (int)n_batch,
+                     (long long)stride_t, (long long)stride_b, N, (const double*)table, B, (const double*)h->e0_dev,
+                     h->e0_mats == 1 ? 0ll : (long long)D, pairs ? 0 : 1, out_dev, stride);
+  HIPCHK(hipGetLastError());
+  h->stats.n_launches++;
+  return RYD_OK;
+}
+
 extern "C" int ryd_ket_to_dm(ryd_handle* h, const void* psi_dev, void* rho_dev, void* stream) {
   if (!h || !psi_dev || !rho_dev) return fail(RYD_ERR_INVALID, "null argument");
   if (h->general) return fail(RYD_ERR_INVALID, "not available on a general-path handle");

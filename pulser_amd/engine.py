@@ -541,6 +541,42 @@ class Engine:
                 "correlation": o[:, n + 1:n + 1 + n * n].reshape(self.batch, n, n),
                 "energy": o[:, n * n + n + 1], "energy2": o[:, n * n + n + 2]}
 
+    def observe_many(self, states: Any, times: Any, occupation: bool = True, correlation: bool = True,
+                     energy: bool = True) -> dict[str, np.ndarray]:
+        """``ryd_observe_many``: what ``observe`` returns, for the kets of every evaluation time of a run in one device
+        call (a memset and at most three launches) and one device-to-host copy.  ``states`` is a complex128 tensor
+        ``[T, B, D]`` on this engine's device, or any view of one whose last axis is contiguous: the strides of the
+        first two axes are passed on, so ``dev[:, b:b + 1]`` of a snapshot tensor is observed in place.  ``times``
+        [T] (us) need not be sorted or distinct.  ``B`` is this engine's batch (entry b has problem b) or anything
+        when the batch is 1 (the one problem serves every entry).  Two-level Ising sesolve engines only.  Returns host
+        arrays ``norm2`` [T, B], ``occupation`` [T, B, N], ``correlation`` [T, B, N, N], ``energy`` [T, B],
+        ``energy2`` [T, B] - NOT normalised (divide by ``norm2``); what was not asked for is 0."""
+        torch = self.torch
+        if not (isinstance(states, torch.Tensor) and states.is_cuda and states.device == self.device):
+            raise ValueError(f"states must be a torch tensor on {self.device}")
+        if states.dtype != torch.complex128:
+            raise ValueError(f"states must be complex128, got {states.dtype}")
+        if states.dim() != 3 or int(states.shape[2]) != self.dim or int(states.shape[1]) < 1:
+            raise ValueError(f"states must have the shape [T, B >= 1, {self.dim}], got {tuple(states.shape)}")
+        if states.stride(2) != 1:
+            raise ValueError("the last axis of states must be contiguous (the first two may be strided)")
+        n_t, n_b = int(states.shape[0]), int(states.shape[1])
+        tt = np.ascontiguousarray(times, dtype=np.float64)
+        if tt.shape != (n_t,):
+            raise ValueError(f"need one time per state of the first axis ({n_t}), got {tt.shape}")
+        # (the stride of an axis of length 1 is arbitrary in torch and never used: any valid value will do)
+        stride_b = int(states.stride(1)) if n_b > 1 else self.dim
+        stride_t = int(states.stride(0)) if n_t > 1 else max(n_b * stride_b, self.dim)
+        n = self.n
+        what = (1 if occupation else 0) | (2 if correlation else 0) | (4 if energy else 0)
+        out = torch.empty((n_t, n_b, n * n + n + 3), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.ryd_observe_many(self._h, states.data_ptr(), n_t, n_b, stride_t, stride_b, tt.ctypes.data,
+                                             what, out.data_ptr(), self._stream()))
+        o = out.cpu().numpy()
+        return {"occupation": o[:, :, :n], "norm2": o[:, :, n],
+                "correlation": o[:, :, n + 1:n + 1 + n * n].reshape(n_t, n_b, n, n),
+                "energy": o[:, :, n * n + n + 1], "energy2": o[:, :, n * n + n + 2]}
+
     def occupations(self, state: Any) -> Any:
         """float64[B, N+1]: <n_k> and, last, the squared norm / trace."""
         self._check_state(state)
