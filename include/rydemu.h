@@ -420,7 +420,7 @@ int ryd_observe(ryd_handle* h, const void* state_dev, double t, int32_t what,
  *               does (a time on a knot belongs to the interval that starts there, the last knot to the last interval).
  *   out_dev     float64[n_times][n_batch][N*N + N + 3], the layout of ryd_observe.  Entries that `what` does not ask
  *               for are 0; the squared norm (slot N) is always written.
- * <H> and <H^2> come from w = H x formed tile by tile inside the reduction (k_observe_many.hpp): no generator
+ * <H> and <H^2> come from w = H x formed tile by tile inside the reduction (k_obs_energy_many, k_observe.hpp): no generator
  * application, no work vector - ryd_stats.n_applications does not move, n_launches counts the launches made.  Agrees
  * with ryd_observe within rounding (different summation order; atomics may move the last bits between calls).
  * n_times = 0 returns RYD_OK and launches nothing.  Scratch for the coefficient table of all times is owned by the

@@ -104,6 +104,33 @@ __device__ __forceinline__ cplx cfma(cplx a, cplx b, cplx c) {  // a*b + c
                       fma(a.x, b.y, fma(a.y, b.x, c.y)));
 }
 
+// The cubic of series `series` on knot interval `idx` at offset u into it; pp: [n_series][n_int][4] complex, highest
+// power first (Horner: three FMAs per component).
+__device__ __forceinline__ cplx pp_eval(const cplx* pp, int n_int, int series, int idx, double u) {
+  const cplx* p = pp + ((size_t)series * n_int + idx) * 4;
+  cplx r = p[0];
+  r = make_double2(fma(r.x, u, p[1].x), fma(r.y, u, p[1].y));
+  r = make_double2(fma(r.x, u, p[2].x), fma(r.y, u, p[2].y));
+  r = make_double2(fma(r.x, u, p[3].x), fma(r.y, u, p[3].y));
+  return r;
+}
+
+// Drive (cr + i ci) and detuning (dl) of one atom: w1 * val(idx1, u1) + w2 * val(idx2, u2) of its drive, detuning and
+// offset series, each times its scale.  Extra detuning terms (ryd_qdesc.extra) are the caller's.
+__device__ __forceinline__ void qdesc_coefs(const cplx* pp, int n_int, const ryd_qdesc d, int idx1, double u1, double w1,
+                                            int idx2, double u2, double w2, double& cr, double& ci, double& dl) {
+  cr = ci = dl = 0.0;
+  if (d.drive_series >= 0) {
+    const cplx a = pp_eval(pp, n_int, d.drive_series, idx1, u1), b = pp_eval(pp, n_int, d.drive_series, idx2, u2);
+    cr = d.drive_scale * (w1 * a.x + w2 * b.x);
+    ci = d.drive_scale * (w1 * a.y + w2 * b.y);
+  }
+  if (d.det_series >= 0)
+    dl += d.det_scale * (w1 * pp_eval(pp, n_int, d.det_series, idx1, u1).x + w2 * pp_eval(pp, n_int, d.det_series, idx2, u2).x);
+  if (d.off_series >= 0)
+    dl += d.off_scale * (w1 * pp_eval(pp, n_int, d.off_series, idx1, u1).x + w2 * pp_eval(pp, n_int, d.off_series, idx2, u2).x);
+}
+
 // wave-uniform double -> scalar registers
 __device__ __forceinline__ double uniform_d(double v) {
   const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));

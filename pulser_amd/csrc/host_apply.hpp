@@ -13,6 +13,16 @@ static int find_interval(const ryd_handle* h, double t) {
   return std::min(std::max(i, 0), n_int - 1);
 }
 
+// one time, weight 1
+static MixPoint mix_at(const ryd_handle* h, double t) {
+  MixPoint m;
+  m.idx1 = m.idx2 = find_interval(h, t);
+  m.u1 = m.u2 = t - h->tknots[m.idx1];
+  m.w1 = 1.0;
+  m.w2 = 0.0;
+  return m;
+}
+
 static int launch_eval(ryd_handle* h, const MixPoint& m, hipStream_t st) {
   const int total = h->B * h->N;
   hipLaunchKernelGGL(k_eval_coefs, dim3((total + 3) / 4), dim3(256), 0, st, h->pp_dev,
@@ -188,11 +198,7 @@ extern "C" int ryd_apply_generator(ryd_handle* h, const void* in_dev, void* out_
     return fail(RYD_ERR_INVALID, "in/out must be distinct non-null device pointers");
   HIPCHK(hipSetDevice(h->cfg.device));
   hipStream_t st = (hipStream_t)stream;
-  MixPoint m;
-  m.idx1 = m.idx2 = find_interval(h, t);
-  m.u1 = m.u2 = t - h->tknots[m.idx1];
-  m.w1 = 1.0;
-  m.w2 = 0.0;
+  const MixPoint m = mix_at(h, t);
   if (h->general) {
     if ((rc = launch_eval_general(h, m, st))) return rc;
     return apply_general(h, m, (const cplx*)in_dev, nullptr, (cplx*)out_dev, 1.0, st);

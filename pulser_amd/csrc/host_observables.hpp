@@ -45,19 +45,14 @@ extern "C" int ryd_observe(ryd_handle* h, const void* state_dev, double t, int32
   HIPCHK(hipMemsetAsync(out_dev, 0, (size_t)h->B * stride * sizeof(double), st));
   const size_t D = (size_t)1 << N;
   if (what & (RYD_OBS_OCCUPATION | RYD_OBS_CORRELATION)) {
-    hipLaunchKernelGGL(k_obs_pairs, dim3((unsigned)((D + 2047) / 2048), h->B), dim3(256), 0, st,
-                       (const cplx*)state_dev, N, dm ? 1 : 0, what, out_dev, stride);
+    hipLaunchKernelGGL(k_obs_pairs, dim3((unsigned)((D + 2047) / 2048), h->B), dim3(256), 0, st, (const cplx*)state_dev,
+                       (long long)h->B, h->B, 0ll, (long long)(dm ? D * D : D), N, dm ? 1 : 0, (int)what, out_dev, stride);
     HIPCHK(hipGetLastError());
     h->stats.n_launches++;
   }
   if (what & RYD_OBS_ENERGY) {
     if (!h->bounds_valid) compute_bounds(h);
-    MixPoint m;
-    m.idx1 = m.idx2 = find_interval(h, t);
-    m.u1 = m.u2 = t - h->tknots[m.idx1];
-    m.w1 = 1.0;
-    m.w2 = 0.0;
-    if ((rc = launch_eval(h, m, st))) return rc;
+    if ((rc = launch_eval(h, mix_at(h, t), st))) return rc;
     if (dm) {
       // Tr(H rho), Tr(H^2 rho) from the elements of rho within two bit flips of the diagonal
       const unsigned nblk = (unsigned)std::min<size_t>(std::max<size_t>(D >> 8, 1), 1024);
@@ -75,7 +70,7 @@ extern "C" int ryd_observe(ryd_handle* h, const void* state_dev, double t, int32
       return rc;
     const unsigned nblk = (unsigned)std::min<size_t>(std::max<size_t>(D >> 10, 1), 1024);
     hipLaunchKernelGGL(k_obs_energy, dim3(nblk, h->B), dim3(256), 0, st, (const cplx*)state_dev,
-                       (const cplx*)h->wA, h->nb, out_dev, stride, N * N + N + 1);
+                       (const cplx*)h->wA, D, out_dev, stride, N * N + N + 1);
     HIPCHK(hipGetLastError());
     h->stats.n_launches++;
   }
@@ -121,16 +116,12 @@ extern "C" int ryd_general_observe(ryd_handle* h, const void* state_dev, double 
     h->stats.n_launches++;
   }
   if (!(what & RYD_OBS_ENERGY)) return RYD_OK;
-  MixPoint m;
-  m.idx1 = m.idx2 = find_interval(h, t);
-  m.u1 = m.u2 = t - h->tknots[m.idx1];
-  m.w1 = 1.0;
-  m.w2 = 0.0;
+  const MixPoint m = mix_at(h, t);
   if ((rc = launch_eval_general(h, m, st))) return rc;
   if (!dm) {
     if ((rc = apply_general(h, m, (const cplx*)state_dev, nullptr, h->wA, 1.0, st))) return rc;
     const unsigned nblk = (unsigned)std::min<size_t>(std::max<size_t>(D >> 10, 1), 1024);
-    hipLaunchKernelGGL(k_gen_obs_energy, dim3(nblk, B), dim3(256), 0, st, (const cplx*)state_dev, (const cplx*)h->wA, D,
+    hipLaunchKernelGGL(k_obs_energy, dim3(nblk, B), dim3(256), 0, st, (const cplx*)state_dev, (const cplx*)h->wA, D,
                        out_dev, stride, off);
     HIPCHK(hipGetLastError());
     h->stats.n_launches++;
@@ -172,7 +163,7 @@ extern "C" int ryd_general_observe(ryd_handle* h, const void* state_dev, double 
   return RYD_OK;
 }
 
-// ryd_observe for every evaluation time of a run (two-level Ising kets): k_observe_many.hpp
+// ryd_observe for every evaluation time of a run (two-level Ising kets): the second half of k_observe.hpp
 extern "C" int ryd_observe_many(ryd_handle* h, const void* states_dev, int32_t n_times, int32_t n_batch,
                                 int64_t stride_t, int64_t stride_b, const double* times, int32_t what,
                                 double* out_dev, void* stream) {
@@ -203,9 +194,8 @@ extern "C" int ryd_observe_many(ryd_handle* h, const void* states_dev, int32_t n
   const unsigned gy = (unsigned)std::min<long long>(n_states, 65535);
   const bool pairs = (what & (RYD_OBS_OCCUPATION | RYD_OBS_CORRELATION)) || !(what & RYD_OBS_ENERGY);
   if (pairs) {
-    hipLaunchKernelGGL(k_obs_pairs_many, dim3((unsigned)((D + 2047) / 2048), gy), dim3(256), 0, st,
-                       (const cplx*)states_dev, n_states, (int)n_batch, (long long)stride_t, (long long)stride_b, N, (int)what,
-                       out_dev, stride);
+    hipLaunchKernelGGL(k_obs_pairs, dim3((unsigned)((D + 2047) / 2048), gy), dim3(256), 0, st, (const cplx*)states_dev,
+                       n_states, (int)n_batch, (long long)stride_t, (long long)stride_b, N, 0, (int)what, out_dev, stride);
     HIPCHK(hipGetLastError());
     h->stats.n_launches++;
   }
@@ -232,10 +222,8 @@ extern "C" int ryd_observe_many(ryd_handle* h, const void* states_dev, int32_t n
     h->obs_many_pin_cap = (size_t)n_times;
   }
   for (int i = 0; i < n_times; ++i) {
-    const int idx = find_interval(h, times[i]);
-    h->obs_many_pin[i].idx = idx;
-    h->obs_many_pin[i].u = times[i] - h->tknots[idx];
-    h->obs_many_pin[i].pad = 0;
+    const MixPoint m = mix_at(h, times[i]);
+    h->obs_many_pin[i] = {m.u1, m.idx1, 0};
   }
   ObsManyTime* tm_dev = (ObsManyTime*)h->obs_many_dev;
   double* table = (double*)((char*)h->obs_many_dev + tm_bytes);

@@ -226,15 +226,7 @@ __global__ __launch_bounds__(256) void k_gen_coefs_fused(const cplx* __restrict_
   for (int t = threadIdx.x; t < n_terms; t += blockDim.x) {
     cplx v = make_double2(w1 + w2, 0.0);
     if (series[t] >= 0) {
-      auto val = [&](double u) -> cplx {
-        const cplx* p = pp + ((size_t)series[t] * n_int + idx) * 4;
-        cplx r = p[0];
-        r = make_double2(fma(r.x, u, p[1].x), fma(r.y, u, p[1].y));
-        r = make_double2(fma(r.x, u, p[2].x), fma(r.y, u, p[2].y));
-        r = make_double2(fma(r.x, u, p[3].x), fma(r.y, u, p[3].y));
-        return r;
-      };
-      const cplx a = val(u1), b = val(u2);
+      const cplx a = pp_eval(pp, n_int, series[t], idx, u1), b = pp_eval(pp, n_int, series[t], idx, u2);
       v = make_double2(w1 * a.x + w2 * b.x, w1 * a.y + w2 * b.y);
       if (conjf[t]) v.y = -v.y;
     }
@@ -429,15 +421,7 @@ __global__ void k_gen_coefs(const cplx* __restrict__ pp, int n_int, const int* _
   if (t >= n_terms) return;
   cplx v = make_double2(w1 + w2, 0.0);
   if (series[t] >= 0) {
-    auto val = [&](double u) -> cplx {
-      const cplx* p = pp + ((size_t)series[t] * n_int + idx) * 4;
-      cplx r = p[0];
-      r = make_double2(fma(r.x, u, p[1].x), fma(r.y, u, p[1].y));
-      r = make_double2(fma(r.x, u, p[2].x), fma(r.y, u, p[2].y));
-      r = make_double2(fma(r.x, u, p[3].x), fma(r.y, u, p[3].y));
-      return r;
-    };
-    const cplx a = val(u1), b = val(u2);
+    const cplx a = pp_eval(pp, n_int, series[t], idx, u1), b = pp_eval(pp, n_int, series[t], idx, u2);
     v = make_double2(w1 * a.x + w2 * b.x, w1 * a.y + w2 * b.y);
     if (conjf[t]) v.y = -v.y;
   }
@@ -539,15 +523,7 @@ __device__ __forceinline__ void gen_traj_body(const GenTrajArgs& A, const GenMcT
       cplx va = make_double2(A.a1 + A.a2, 0.0), vb = va;
       const int ser = A.series[tid];
       if (ser >= 0) {
-        auto val = [&](double u) -> cplx {
-          const cplx* p = A.pp + ((size_t)ser * A.n_int + sd.idx) * 4;
-          cplx r = p[0];
-          r = make_double2(fma(r.x, u, p[1].x), fma(r.y, u, p[1].y));
-          r = make_double2(fma(r.x, u, p[2].x), fma(r.y, u, p[2].y));
-          r = make_double2(fma(r.x, u, p[3].x), fma(r.y, u, p[3].y));
-          return r;
-        };
-        const cplx a = val(sd.u1), b = val(sd.u2);
+        const cplx a = pp_eval(A.pp, A.n_int, ser, sd.idx, sd.u1), b = pp_eval(A.pp, A.n_int, ser, sd.idx, sd.u2);
         va = make_double2(A.a1 * a.x + A.a2 * b.x, A.a1 * a.y + A.a2 * b.y);
         vb = make_double2(A.a2 * a.x + A.a1 * b.x, A.a2 * a.y + A.a1 * b.y);
         if (A.conjf[tid]) { va.y = -va.y; vb.y = -vb.y; }

@@ -1,39 +1,29 @@
 // Part of librydemu (included by rydemu.hip, one translation unit).
 // ---------------------------------------------------------------------------
-// ryd_observe: the V2 observables of one state in one call, on the device
+// ryd_observe: the V2 observables of one state in one call, on the device (ryd_observe_many: second half of the file)
 // ---------------------------------------------------------------------------
 // Occupations <n_k>, correlations <n_k n_l> (default_observables.py:291-435) and the energy
 // moments <H>, <H^2> (:437-580, through one generator application w = -i H x:
 // <H> = -Im <x|w>, <H^2> = |w|^2).  Replaces N(N+1)/2 + 2 qutip.expect calls and the per-time
 // materialisation of H(t) (qutip_backend.py:259-264).
 
-// out[b][0..N-1] = <n_k>, out[b][N] = sum p, out[b][N+1 + k*N + l] = <n_k n_l>.
-// One block stages a chunk of probabilities in LDS; thread <-> (k, l) pair (several per thread when
-// N(N+1)/2 > blockDim); wave-uniform chunk index -> LDS broadcast reads.  `what`: RYD_OBS_OCCUPATION and / or
-// RYD_OBS_CORRELATION - the slots of the one not asked for stay 0 (the norm is written with either).
-__global__ __launch_bounds__(256) void k_obs_pairs(const cplx* __restrict__ st, int N, int is_dm, int what,
-                                                   double* __restrict__ out, int out_stride) {
-  constexpr int CH = 2048;
-  __shared__ double ps[CH];
-  const size_t D = (size_t)1 << N;
-  const int b = blockIdx.y;
+// The pair sums of one staged chunk, shared by every pair kernel: ps[i] is the probability of chunk element i (0 past the
+// end of the state), o the output row: o[0..N-1] += <n_k>, o[N] += sum p, o[N+1 + k*N + l] += <n_k n_l>.
+// thread <-> (k <= l) pair (several per thread when N(N+1)/2 >= blockDim), one more for the norm; the chunk index is
+// wave-uniform -> LDS broadcast reads; one atomic per pair and block.  `what`: RYD_OBS_OCCUPATION and / or
+// RYD_OBS_CORRELATION - the slots of the one not asked for stay 0, and with neither only the norm is written.
+// "Atoms k and l of element i are in the one-state" - DIGITS = false: bits N-1-k and N-1-l of the index base + i are 0
+// (two-level registers: n = 1 <=> bit 0, local state 0 = r); DIGITS = true: bits k and l of the staged word wd[i] are set.
+constexpr int kObsCH = 2048;
+
+template <bool DIGITS>
+__device__ __forceinline__ void obs_pair_sums(const double* ps, const unsigned* wd, size_t base, int N, int what,
+                                              double* __restrict__ o) {
   const int npair = N * (N + 1) / 2;
-  const size_t base = (size_t)blockIdx.x * CH;
-  for (int i = threadIdx.x; i < CH; i += blockDim.x) {
-    const size_t g = base + i;
-    double p = 0.0;
-    if (g < D) {
-      if (is_dm) p = st[((size_t)b << (2 * N)) + g * D + g].x;
-      else { const cplx v = st[((size_t)b << N) + g]; p = v.x * v.x + v.y * v.y; }
-    }
-    ps[i] = p;
-  }
-  __syncthreads();
-  double* o = out + (size_t)b * out_stride;
   for (int pr = threadIdx.x; pr <= npair; pr += blockDim.x) {
     if (pr == npair) {  // the norm
       double s = 0.0;
-      for (int i = 0; i < CH; ++i) s += ps[i];
+      for (int i = 0; i < kObsCH; ++i) s += ps[i];
       atomicAdd(o + N, s);
       continue;
     }
@@ -42,12 +32,11 @@ __global__ __launch_bounds__(256) void k_obs_pairs(const cplx* __restrict__ st, 
     while (rem >= N - k) { rem -= N - k; ++k; }
     const int l = k + rem;
     if (k != l && !(what & RYD_OBS_CORRELATION)) continue;
-    const unsigned mk = 1u << (N - 1 - k), ml = 1u << (N - 1 - l);
+    if (k == l && !(what & (RYD_OBS_OCCUPATION | RYD_OBS_CORRELATION))) continue;
+    const unsigned m = DIGITS ? (1u << k) | (1u << l) : (1u << (N - 1 - k)) | (1u << (N - 1 - l));
     double s = 0.0;
-    for (int i = 0; i < CH; ++i) {
-      const unsigned g = (unsigned)(base + i);
-      if (!(g & mk) && !(g & ml)) s += ps[i];  // n = 1 <=> bit 0 (local state 0 = r)
-    }
+    for (int i = 0; i < kObsCH; ++i)
+      if (DIGITS ? (wd[i] & m) == m : !((unsigned)(base + i) & m)) s += ps[i];
     if (k == l && (what & RYD_OBS_OCCUPATION)) atomicAdd(o + k, s);
     if (!(what & RYD_OBS_CORRELATION)) continue;
     atomicAdd(o + N + 1 + k * N + l, s);
@@ -55,10 +44,37 @@ __global__ __launch_bounds__(256) void k_obs_pairs(const cplx* __restrict__ st, 
   }
 }
 
-// o[0] += -Im <x|w>, o[1] += |w|^2
-__global__ __launch_bounds__(256) void k_obs_energy(const cplx* __restrict__ x, const cplx* __restrict__ w, int nb,
+// Row s of out ([out_stride] doubles, laid out as above) for state s = it * n_batch + b at states + it * stride_t +
+// b * stride_b (64-bit offsets), the states taken from the second grid axis with a stride (it is capped at 65 535
+// workgroups).  One block stages a chunk of probabilities in LDS: |x_g|^2 of a ket, Re rho_gg of a density matrix
+// (is_dm: stride_b = D * D).  ryd_observe: n_states = n_batch = its batch.
+__global__ __launch_bounds__(256) void k_obs_pairs(const cplx* __restrict__ states, long long n_states, int n_batch,
+                                                   long long stride_t, long long stride_b, int N, int is_dm, int what,
+                                                   double* __restrict__ out, int out_stride) {
+  __shared__ double ps[kObsCH];
+  const size_t D = (size_t)1 << N;
+  const size_t base = (size_t)blockIdx.x * kObsCH;
+  for (long long s = blockIdx.y; s < n_states; s += gridDim.y) {
+    const long long it = s / n_batch, b = s - it * n_batch;
+    const cplx* st = states + it * stride_t + b * stride_b;
+    for (int i = threadIdx.x; i < kObsCH; i += blockDim.x) {
+      const size_t g = base + i;
+      double p = 0.0;
+      if (g < D) {
+        if (is_dm) p = st[g * (D + 1)].x;
+        else { const cplx v = st[g]; p = v.x * v.x + v.y * v.y; }
+      }
+      ps[i] = p;
+    }
+    __syncthreads();
+    obs_pair_sums<false>(ps, nullptr, base, N, what, out + (size_t)s * out_stride);
+    __syncthreads();  // `ps` is filled again for the next state of this workgroup
+  }
+}
+
+// o[0] += -Im <x|w>, o[1] += |w|^2 over vectors of any length D: wave64 shuffles, one atomic pair per wave.
+__global__ __launch_bounds__(256) void k_obs_energy(const cplx* __restrict__ x, const cplx* __restrict__ w, size_t D,
                                                     double* __restrict__ out, int out_stride, int off) {
-  const size_t D = (size_t)1 << nb;
   const size_t boff = (size_t)blockIdx.y * D;
   double e = 0.0, e2 = 0.0;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < D; i += (size_t)gridDim.x * 256) {
@@ -126,5 +142,123 @@ __global__ __launch_bounds__(256) void k_obs_energy_dm(const cplx* __restrict__ 
   if ((threadIdx.x & 63) == 0) {
     atomicAdd(out + (size_t)b * out_stride + off, e1);
     atomicAdd(out + (size_t)b * out_stride + off + 1, e2);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// ryd_observe_many: the V2 observables of EVERY evaluation time of a run in one call
+// ---------------------------------------------------------------------------
+// ryd_observe serves one state per call: the backend uploaded each state, ran five launches and read
+// the result back, once per evaluation time (3 101 times for a 14-atom run with evaluation_times="Full").  The
+// snapshots of a solve are one device tensor already, so the same numbers for all of them are a memset and at most
+// three launches.  Two-level Ising kets only.  State s = i * n_batch + b of the call lives at
+// states + i * stride_t + b * stride_b (64-bit offsets: 3 101 x 2^14 amplitudes exceed 2^31 bytes), is observed with
+// the coefficients of row (i, hb) of the table below, hb = b when the handle has one problem per entry and 0 when its
+// one problem serves every entry, and writes row s of out ([N*N + N + 3] doubles, the layout of ryd_observe).
+// The second grid axis is the state; it is capped at 65 535 workgroups, so every kernel strides over s.
+
+// One (interval, offset into it) per evaluation time, found on the host exactly as ryd_observe finds it.
+struct ObsManyTime {
+  double u;
+  int idx;
+  int pad;
+};
+
+// coefs[i][hb][k] = (Re c, Im c, delta, 0) of atom k at time i, one thread per (i, hb, k): qdesc_coefs at one time with
+// weight 1, as k_eval_coefs evaluates it (there a wave per entry shares the list of extra detuning terms; that list is
+// not evaluated here: ryd_observe_many refuses handles that carry one).
+__global__ __launch_bounds__(256) void k_eval_coefs_many(const cplx* __restrict__ pp, int n_int,
+                                                         const ryd_qdesc* __restrict__ desc,
+                                                         const ObsManyTime* __restrict__ tm, int per_time,
+                                                         long long total, double* __restrict__ coefs) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const long long it = i / per_time;
+  const ryd_qdesc d = desc[i - it * per_time];
+  const int idx = tm[it].idx;
+  const double u = tm[it].u;
+  double cr, ci, dl;
+  qdesc_coefs(pp, n_int, d, idx, u, 1.0, idx, u, 0.0, cr, ci, dl);
+  coefs[4 * (size_t)i + 0] = cr;
+  coefs[4 * (size_t)i + 1] = ci;
+  coefs[4 * (size_t)i + 2] = dl;
+  coefs[4 * (size_t)i + 3] = 0.0;
+}
+
+// <H> and <H^2> of a ket without writing w = H x anywhere: one workgroup stages a tile of 2^TB consecutive amplitudes
+// of one state in LDS and forms, for each of them,
+//   w_a = (e0[a] - sum_{k: bit_k(a) = 0} delta_k) x_a + sum_k h_k(a) x_{a ^ k},   h_k(a) = bit_k(a) ? c_k : conj(c_k)
+// (atom k on bit N-1-k: the conventions of k_obs_energy_dm and k_build_e0).  The partner of a flip of one of the low TB
+// bits is in the tile (one 16-byte LDS read, consecutive lanes on consecutive slots); the partner of a higher bit is
+// the same slot of another tile, a coalesced 16-byte load that L2 serves (a 14-atom ket is 256 KiB).  Re(conj(x_a) w_a)
+// and |w_a|^2 stay in registers, go through __shfl_down and then LDS across the four waves, and leave as one fp64
+// atomicAdd pair per workgroup (the pattern of k_obs_energy / k_expect_sparse).  TB = 11: 32 KiB of LDS, so four
+// workgroups share a CU, and a 14-atom state is 8 workgroups - 3 101 states fill the 256 CUs many times over, while
+// only 3 of the 14 partners of an amplitude come from outside the tile.  Registers of fewer than TB atoms fill a part
+// of the tile and load no partner from global memory.  `with_norm`: also out[s][N] += sum |x_a|^2 (energy-only calls,
+// where k_obs_pairs does not run).
+constexpr int kObsManyTB = 11;
+
+__global__ __launch_bounds__(256) void k_obs_energy_many(const cplx* __restrict__ states, long long n_states,
+                                                         int n_batch, long long stride_t, long long stride_b, int N,
+                                                         const double* __restrict__ coefs, int handle_batch,
+                                                         const double* __restrict__ e0, long long e0_stride,
+                                                         int with_norm, double* __restrict__ out, int out_stride) {
+  constexpr int TILE = 1 << kObsManyTB;
+  __shared__ cplx tile[TILE];
+  __shared__ double cf[4 * RYD_MAX_QUBITS];
+  __shared__ double part[4][3];
+  const size_t D = (size_t)1 << N;
+  const size_t a0 = (size_t)blockIdx.x * TILE;
+  const int n_in = (int)(D - a0 < (size_t)TILE ? D - a0 : (size_t)TILE);  // amplitudes of this tile (D < TILE: all of them)
+  const int off = N * N + N + 1;
+  for (long long s = blockIdx.y; s < n_states; s += gridDim.y) {
+    const long long it = s / n_batch, b = s - it * n_batch;
+    const long long hb = handle_batch == 1 ? 0 : b;
+    const cplx* st = states + it * stride_t + b * stride_b;
+    const double* cfg = coefs + ((size_t)it * handle_batch + hb) * N * 4;
+    const double* e0b = e0 + hb * e0_stride;
+    for (int i = threadIdx.x; i < n_in; i += 256) tile[i] = st[a0 + i];
+    for (int i = threadIdx.x; i < 4 * N; i += 256) cf[i] = cfg[i];
+    __syncthreads();
+    double e1 = 0.0, e2 = 0.0, nrm = 0.0;
+    for (int i = threadIdx.x; i < n_in; i += 256) {
+      const size_t a = a0 + i;
+      const cplx x = tile[i];
+      double diag = e0b[a];
+      double wx = 0.0, wy = 0.0;
+      for (int k = 0; k < N; ++k) {
+        const int p = N - 1 - k;
+        const bool bit = (a >> p) & 1;
+        const double cr = cf[4 * k], ci = bit ? cf[4 * k + 1] : -cf[4 * k + 1];
+        if (!bit) diag -= cf[4 * k + 2];
+        const cplx y = p < kObsManyTB ? tile[i ^ (1 << p)] : st[a ^ ((size_t)1 << p)];
+        wx += cr * y.x - ci * y.y;
+        wy += cr * y.y + ci * y.x;
+      }
+      wx = fma(diag, x.x, wx);
+      wy = fma(diag, x.y, wy);
+      e1 += x.x * wx + x.y * wy;
+      e2 = fma(wx, wx, fma(wy, wy, e2));
+      nrm = fma(x.x, x.x, fma(x.y, x.y, nrm));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      e1 += __shfl_down(e1, o, 64);
+      e2 += __shfl_down(e2, o, 64);
+      nrm += __shfl_down(nrm, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      part[threadIdx.x >> 6][0] = e1;
+      part[threadIdx.x >> 6][1] = e2;
+      part[threadIdx.x >> 6][2] = nrm;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && (threadIdx.x < 2 || with_norm)) {
+      const int j = threadIdx.x;
+      const double v = (part[0][j] + part[1][j]) + (part[2][j] + part[3][j]);
+      atomicAdd(out + (size_t)s * out_stride + (j < 2 ? off + j : N), v);
+    }
+    __syncthreads();  // `tile`, `cf` and `part` are written again for the next state of this workgroup
   }
 }

@@ -13,32 +13,14 @@ __global__ __launch_bounds__(256) void k_eval_coefs(const cplx* __restrict__ pp,
   const int lane = threadIdx.x & 63;
   if (i >= total) return;
   const ryd_qdesc d = desc[i];
-  auto val = [&](int s, int idx, double u) -> cplx {
-    const cplx* p = pp + ((size_t)s * n_int + idx) * 4;
-    cplx r = p[0];
-    r = make_double2(fma(r.x, u, p[1].x), fma(r.y, u, p[1].y));
-    r = make_double2(fma(r.x, u, p[2].x), fma(r.y, u, p[2].y));
-    r = make_double2(fma(r.x, u, p[3].x), fma(r.y, u, p[3].y));
-    return r;
-  };
   double cr = 0, ci = 0, dl = 0;
-  if (lane == 0) {
-    if (d.drive_series >= 0) {
-      const cplx a = val(d.drive_series, idx1, u1), b2 = val(d.drive_series, idx2, u2);
-      cr = d.drive_scale * (w1 * a.x + w2 * b2.x);
-      ci = d.drive_scale * (w1 * a.y + w2 * b2.y);
-    }
-    if (d.det_series >= 0)
-      dl += d.det_scale * (w1 * val(d.det_series, idx1, u1).x + w2 * val(d.det_series, idx2, u2).x);
-    if (d.off_series >= 0)
-      dl += d.off_scale * (w1 * val(d.off_series, idx1, u1).x + w2 * val(d.off_series, idx2, u2).x);
-  }
+  if (lane == 0) qdesc_coefs(pp, n_int, d, idx1, u1, w1, idx2, u2, w2, cr, ci, dl);
   if (d.extra > 0 && dterms) {  // high-frequency detuning noise on shared series
     const int count = dterms[d.extra - 1].remaining + 1;
     double x = 0.0;
     for (int e = lane; e < count; e += 64) {
       const ryd_dterm t = dterms[d.extra - 1 + e];
-      x += t.scale * (w1 * val(t.series, idx1, u1).x + w2 * val(t.series, idx2, u2).x);
+      x += t.scale * (w1 * pp_eval(pp, n_int, t.series, idx1, u1).x + w2 * pp_eval(pp, n_int, t.series, idx2, u2).x);
     }
     for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
     dl += x;

@@ -91,14 +91,7 @@ __global__ __launch_bounds__(256) void k_split_coefs(const cplx* __restrict__ pp
   const double beta = snap_close ? 0.0 : closing ? R.kick_post : splitrun_b(R, s, st) * R.tau[s];
 
   const ryd_qdesc d = desc[i];
-  auto val = [&](int sr, int idx, double u) -> cplx {
-    const cplx* p = pp + ((size_t)sr * n_int + idx) * 4;
-    cplx r = p[0];
-    r = make_double2(fma(r.x, u, p[1].x), fma(r.y, u, p[1].y));
-    r = make_double2(fma(r.x, u, p[2].x), fma(r.y, u, p[2].y));
-    r = make_double2(fma(r.x, u, p[3].x), fma(r.y, u, p[3].y));
-    return r;
-  };
+  auto val = [&](int sr, int idx, double u) { return pp_eval(pp, n_int, sr, idx, u); };
   double dl = 0.0;
 #pragma unroll
   for (int q = 0; q < 2; ++q) {

@@ -72,14 +72,7 @@ __global__ __launch_bounds__(NTT) void k_traj_dm(const TrajDmArgs A) {
     const StepDesc sd = A.steps[s];
     if (tid < N) {
       const ryd_qdesc d = A.desc[(size_t)b * N + tid];
-      auto val = [&](int ser, double u) -> cplx {
-        const cplx* p = A.pp + ((size_t)ser * A.n_int + sd.idx) * 4;
-        cplx r = p[0];
-        r = make_double2(fma(r.x, u, p[1].x), fma(r.y, u, p[1].y));
-        r = make_double2(fma(r.x, u, p[2].x), fma(r.y, u, p[2].y));
-        r = make_double2(fma(r.x, u, p[3].x), fma(r.y, u, p[3].y));
-        return r;
-      };
+      auto val = [&](int ser, double u) { return pp_eval(A.pp, A.n_int, ser, sd.idx, u); };
       double c1r = 0, c1i = 0, c2r = 0, c2i = 0, dlA = 0, dlB = 0;
       if (d.drive_series >= 0) {
         const cplx v1 = val(d.drive_series, sd.u1), v2 = val(d.drive_series, sd.u2);

@@ -70,7 +70,6 @@ SPLITR_INSTANCES_13(SPLITR_EXTERN)
 SPLITR_INSTANCES_14(SPLITR_EXTERN)
 #endif
 #include "k_observe.hpp"
-#include "k_observe_many.hpp"
 #include "k_gen_observe.hpp"
 #include "k_expect.hpp"
 #include "k_general.hpp"

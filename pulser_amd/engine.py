@@ -40,6 +40,19 @@ def _method_code(method: str) -> int:
         raise ValueError(f"unknown method {method!r}; one of {sorted(_METHODS)}") from None
 
 
+def _obs_what(occupation: bool, correlation: bool, energy: bool, density: bool = False) -> int:
+    """The RYD_OBS_* bits of the ``what`` argument of the observe calls."""
+    return (1 if occupation else 0) | (2 if correlation else 0) | (4 if energy else 0) | (8 if density else 0)
+
+
+def _obs_unpack(out: Any, n: int) -> dict[str, np.ndarray]:
+    """Host views of the observe calls' output ``[..., N*N + N + 3]`` (any leading axes), by name."""
+    o = out.cpu().numpy()
+    return {"occupation": o[..., :n], "norm2": o[..., n],
+            "correlation": o[..., n + 1:n + 1 + n * n].reshape(*o.shape[:-1], n, n),
+            "energy": o[..., n * n + n + 1], "energy2": o[..., n * n + n + 2]}
+
+
 def outer_accumulate(psi: Any, acc: Any, weights: Any = None) -> None:
     """``acc[D, D] += sum_b w_b |psi_b><psi_b|`` on the device, without a solver handle and for any
     state dimension (``ryd_outer_accumulate_dim``): the trajectory mean of
@@ -532,14 +545,11 @@ class Engine:
         else:
             self._check_state(state)
         n = self.n
-        what = (1 if occupation else 0) | (2 if correlation else 0) | (4 if energy else 0) | (8 if density else 0)
+        what = _obs_what(occupation, correlation, energy, density)
         out = self.torch.empty((self.batch, n * n + n + 3), dtype=self.torch.float64, device=self.device)
         _lib.check(self.lib.ryd_observe(self._h, state.data_ptr(), float(t), what, out.data_ptr(),
                                         self._stream()))
-        o = out.cpu().numpy()
-        return {"occupation": o[:, :n], "norm2": o[:, n],
-                "correlation": o[:, n + 1:n + 1 + n * n].reshape(self.batch, n, n),
-                "energy": o[:, n * n + n + 1], "energy2": o[:, n * n + n + 2]}
+        return _obs_unpack(out, n)
 
     def observe_many(self, states: Any, times: Any, occupation: bool = True, correlation: bool = True,
                      energy: bool = True) -> dict[str, np.ndarray]:
@@ -568,14 +578,11 @@ class Engine:
         stride_b = int(states.stride(1)) if n_b > 1 else self.dim
         stride_t = int(states.stride(0)) if n_t > 1 else max(n_b * stride_b, self.dim)
         n = self.n
-        what = (1 if occupation else 0) | (2 if correlation else 0) | (4 if energy else 0)
+        what = _obs_what(occupation, correlation, energy)
         out = torch.empty((n_t, n_b, n * n + n + 3), dtype=torch.float64, device=self.device)
         _lib.check(self.lib.ryd_observe_many(self._h, states.data_ptr(), n_t, n_b, stride_t, stride_b, tt.ctypes.data,
                                              what, out.data_ptr(), self._stream()))
-        o = out.cpu().numpy()
-        return {"occupation": o[:, :, :n], "norm2": o[:, :, n],
-                "correlation": o[:, :, n + 1:n + 1 + n * n].reshape(n_t, n_b, n, n),
-                "energy": o[:, :, n * n + n + 1], "energy2": o[:, :, n * n + n + 2]}
+        return _obs_unpack(out, n)
 
     def occupations(self, state: Any) -> Any:
         """float64[B, N+1]: <n_k> and, last, the squared norm / trace."""
@@ -887,14 +894,11 @@ class GeneralEngine:
                                  f"{self.device}, got {tuple(state.shape)} {state.dtype} on {state.device}")
         else:
             self._check_batch_state(state, self.batch)
-        what = (1 if occupation else 0) | (2 if correlation else 0) | (4 if energy else 0) | (8 if density else 0)
+        what = _obs_what(occupation, correlation, energy, density)
         out = self.torch.empty((self.batch, n * n + n + 3), dtype=self.torch.float64, device=self.device)
         _lib.check(self.lib.ryd_general_observe(self._h, state.data_ptr(), float(t), what, self.local_dim, n, one,
                                                 out.data_ptr(), self._stream()))
-        o = out.cpu().numpy()
-        return {"occupation": o[:, :n], "norm2": o[:, n],
-                "correlation": o[:, n + 1:n + 1 + n * n].reshape(self.batch, n, n),
-                "energy": o[:, n * n + n + 1], "energy2": o[:, n * n + n + 2]}
+        return _obs_unpack(out, n)
 
     def set_path(self, force_multi_launch: bool, no_sites: bool = False, no_fused: bool = False,
                  observe_small_chunks: bool = False) -> None:

@@ -1,4 +1,4 @@
-"""GPU: ``ryd_general_observe`` (k_gen_observe.hpp: k_gen_obs_pairs, k_gen_obs_energy, k_gen_obs_stage_cols,
+"""GPU: ``ryd_general_observe`` (k_gen_observe.hpp: k_gen_obs_pairs, k_obs_energy, k_gen_obs_stage_cols,
 k_gen_obs_trace) called directly through ``GeneralEngine.observe`` and pinned to the longdouble host references of
 tests/observe_ref.py and tests/general_observe_ref.py, on XY registers (d = 2), the 3-level "all" basis and a 4-level
 leakage register, with complex drives.
@@ -15,7 +15,7 @@ project's 1e-11 bar of one generator application); nothing is fitted to what the
 ``error / tolerance`` before it asserts.  Worst ratios seen on an MI355X, per kernel:
 
     k_gen_obs_pairs        0.082     (the 16-term bound of a 4-atom XY register; below 0.02 from 3^6 amplitudes on)
-    k_gen_obs_energy       1.0e-5    (<H>; <H^2> 8.0e-6)
+    k_obs_energy           1.0e-5    (<H>; <H^2> 8.0e-6)
     k_gen_obs_trace        1.0e-5    (Tr(H rho); Tr(H^2 rho) 1.1e-5; both on a basis state |1><1|)
     apply_generator        3.2e-5    (batched GeneralEngine.apply_generator against the 1e-11 bar)
 """
@@ -119,8 +119,8 @@ def _check_pairs(got, b, ref, D, tag, occupation=True, correlation=True):
 def _check_ket_energy(got, b, ref, x, tag):
     e1, e2, s_abs, w = ref
     tol1, tol2 = tol_energy_ket(x, w, s_abs)
-    ok = _report("k_gen_obs_energy", f"{tag} <H>", abs(got["energy"][b] - e1), tol1)
-    return ok & _report("k_gen_obs_energy", f"{tag} <H^2>", abs(got["energy2"][b] - e2), tol2)
+    ok = _report("k_obs_energy", f"{tag} <H>", abs(got["energy"][b] - e1), tol1)
+    return ok & _report("k_obs_energy", f"{tag} <H^2>", abs(got["energy2"][b] - e2), tol2)
 
 
 def _check_dm_energy(got, b, ham, t, rho, tag):

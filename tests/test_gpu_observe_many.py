@@ -1,4 +1,4 @@
-"""GPU: ``ryd_observe_many`` (k_eval_coefs_many, k_obs_pairs_many, k_obs_energy_many) - the occupations, correlations and
+"""GPU: ``ryd_observe_many`` (k_eval_coefs_many, k_obs_pairs, k_obs_energy_many) - the occupations, correlations and
 energy moments of the kets of every evaluation time in one call - called directly through ``Engine.observe_many`` and
 pinned to the longdouble host reference of tests/observe_ref.py, and its use by ``QutipBackendV2``.
 
@@ -13,7 +13,7 @@ fitted.  The backend cases compare the one-call path with the per-time path with
 written for a normalised state without reading it (``_backend_bounds``).  Every case prints ``error / tolerance``
 before it asserts.  Worst ratios seen on an MI355X:
 
-    k_obs_pairs_many      0.19      (the 4-term norm of a 2-atom ket; below 0.02 from 10 atoms on)
+    k_obs_pairs           0.19      (the 4-term norm of a 2-atom ket; below 0.02 from 10 atoms on)
     k_obs_energy_many     3.0e-05
     300 times, 10 atoms   pair sums identical to per-time ``Engine.observe``; <H> 5.3e-06, <H^2> 3.0e-06 of both bounds
     backend, both paths   occupation 0.015, correlation 0.005, <H> 7.2e-06, <H^2> 3.7e-06
@@ -28,7 +28,7 @@ from observe_ref import U53, ket_probabilities, ref_energy_ket, ref_pairs, tol_e
 
 pytestmark = pytest.mark.gpu
 
-TB = 11                                   # kObsManyTB of k_observe_many.hpp
+TB = 11                                   # kObsManyTB of k_observe.hpp
 T_KNOT, T_LAST = 0.2, 0.4                 # knots 200 and 400 of the 401 of local_problem (1-ns grid)
 TIMES = {1: [0.12345], 2: [T_KNOT, 0.0], 7: [T_LAST, 0.0, 0.12345, T_KNOT, 0.12345, 0.3, 0.05]}
 SCALES = (1.0, 0.6, 1.9)
@@ -93,11 +93,11 @@ def _check_state(got, i, b, x, ham, t, n, tag, occupation=True, correlation=True
     """Every requested output of state (i, b) against the longdouble reference."""
     D = 2**n
     norm, occ, corr, (s_norm, s_occ, s_corr) = ref_pairs(ket_probabilities(x), n)
-    ok = _report("k_obs_pairs_many", f"{tag} norm2", abs(got["norm2"][i, b] - norm), tol_sum(D, s_norm))
+    ok = _report("k_obs_pairs", f"{tag} norm2", abs(got["norm2"][i, b] - norm), tol_sum(D, s_norm))
     if occupation:
-        ok &= _report("k_obs_pairs_many", f"{tag} occupation", np.abs(got["occupation"][i, b] - occ), tol_sum(D, s_occ))
+        ok &= _report("k_obs_pairs", f"{tag} occupation", np.abs(got["occupation"][i, b] - occ), tol_sum(D, s_occ))
     if correlation:
-        ok &= _report("k_obs_pairs_many", f"{tag} correlation", np.abs(got["correlation"][i, b] - corr), tol_sum(D, s_corr))
+        ok &= _report("k_obs_pairs", f"{tag} correlation", np.abs(got["correlation"][i, b] - corr), tol_sum(D, s_corr))
     if energy:
         e1, e2, s_abs, w = ref_energy_ket(ham, t, x)
         tol1, tol2 = tol_energy_ket(x, w, s_abs)
@@ -188,6 +188,45 @@ def test_observe_many_300_times_against_per_time_observe():
     print("RATIO many vs per-time (norm2, occupation, correlation, <H>, <H^2>):", " ".join(f"{v:.3e}" for v in worst))
     for i in (0, 17, 40, 43, 150, 151, 222, 299):
         ok &= _check_state(got, i, 0, xs[i, 0], ham, times[i], n, f"n={n} T=300 i={i} t={times[i]:.5f}")
+    assert ok
+
+
+@pytest.mark.parametrize("what", [dict(), dict(correlation=False, energy=False)], ids=["all", "occupation"])
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("n", [1, 2, 11])
+def test_observe_many_pair_sums_equal_per_time_observe_to_the_bit(n, B, what):
+    """``ryd_observe`` and ``ryd_observe_many`` launch ONE pair kernel (k_obs_pairs).  Up to 11 atoms a state is one chunk
+    of 2 048 probabilities (11 atoms fill it, 1 atom is one pair and padding), so every output slot receives exactly
+    one atomicAdd, the result is deterministic, and the two callers must agree bit for bit."""
+    T = 4
+    times = TIMES[7][:T]
+    with _engine(_problems(n, B)) as eng:
+        dev = _dev(eng, _kets(n, T, B))
+        got = eng.observe_many(dev, times, **what)
+        single = [eng.observe(dev[i], times[i], **what) for i in range(T)]
+    for i, key in itertools.product(range(T), ("occupation", "correlation", "norm2")):
+        assert np.array_equal(got[key][i], single[i][key]), (i, key, got[key][i], single[i][key])
+    if what:
+        assert np.all(got["correlation"] == 0.0) and np.any(got["occupation"] != 0.0)
+
+
+def test_observe_many_pair_sums_against_per_time_observe_two_chunks():
+    """12 atoms: two chunks add into every slot, in either order, so the two callers agree within the sum of their
+    bounds (``tol_sum`` of tests/observe_ref.py) and no bit equality is asserted."""
+    n, B, T = 12, 3, 4
+    D = 2**n
+    times = TIMES[7][:T]
+    xs = _kets(n, T, B)
+    with _engine(_problems(n, B)) as eng:
+        dev = _dev(eng, xs)
+        got = eng.observe_many(dev, times, energy=False)
+        single = [eng.observe(dev[i], times[i], energy=False) for i in range(T)]
+    ok = True
+    for i, b in itertools.product(range(T), range(B)):
+        _, _, _, sums = ref_pairs(ket_probabilities(xs[i, b]), n)
+        for key, s_abs in zip(("norm2", "occupation", "correlation"), sums):
+            ok &= _report("k_obs_pairs", f"n=12 i={i} b={b} {key} many vs per-time",
+                          np.abs(got[key][i, b] - single[i][key][b]), 2 * tol_sum(D, s_abs))
     assert ok
 
 
