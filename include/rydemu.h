@@ -361,7 +361,8 @@ int ryd_general_mc_solve_many(ryd_handle** hs, int32_t n, void* const* states_de
  * inside the run (k_split_reg<.., SNAP> + k_split_snap_close),
  * 262144 = general path: the round-3 site kernel (k_gen_apply_sites) instead of the padded site tables of
  * k_gen_apply_fused (round 6),
- * 524288 = ryd_general_observe on density matrices: 5 columns of rho per chunk (the chunked path without a 1-GiB state).
+ * 524288 = ryd_general_observe on density matrices: 5 columns of rho per chunk (the chunked path without a 1-GiB state);
+ * ryd_general_observe_many: 5 evaluation times per chunk of tables (its chunked path without 256 MiB of them).
  * Never needed for results. */
 int ryd_set_path(ryd_handle* h, int32_t force_generic);
 
@@ -451,6 +452,45 @@ int ryd_observe_many(ryd_handle* h, const void* states_dev, int32_t n_times, int
  *                    it does on a ket handle with collapse operators (H_eff). */
 int ryd_general_observe(ryd_handle* h, const void* state_dev, double t, int32_t what, int32_t local_dim,
                         int32_t n_atoms, int32_t one_digit, double* out_dev, void* stream);
+
+/* ryd_general_observe for every evaluation time of a run in one call: one memset and at most three launches for any
+ * n_times, n_batch and `what`, instead of one upload, about five launches (one of them a full generator application)
+ * and one read-back per time.  Kets of a general-path KET handle; `what`, local_dim, n_atoms and one_digit as for
+ * ryd_general_observe, with the same range checks and dim == local_dim^n_atoms.
+ *   states_dev  complex128, device: state (i, b) starts at states_dev + i * stride_t + b * stride_b (in amplitudes, 64-bit
+ *               offsets; both strides >= dim, else RYD_ERR_INVALID); the dim amplitudes of a state are contiguous.
+ *   n_batch     states per time, any number: a general handle holds ONE problem, which serves every entry (unlike
+ *               ryd_observe_many, where the batch index selects the problem).
+ *   times       host float64[n_times] (us): the H(t) of each time for the energy moments; unsorted, repeated values are fine.
+ *   out_dev     float64[n_times][n_batch][N*N + N + 3], the layout of ryd_general_observe.  Zeroed first; slots not asked
+ *               for are exactly 0; the squared norm (slot N) is always written (by the pair launch, or by the energy
+ *               kernel when no pair launch runs).
+ * Launches: the pair reduction over all states (k_gen_obs_pairs), the tables of all times (k_gen_coefs_fused_many) and
+ * k_gen_obs_energy_many, which forms w = -iHx row block by row block inside the reduction with the site loop of
+ * k_gen_apply_fused - a row's w is the application's own value, w never reaches memory.  ryd_stats.n_applications does
+ * not move, n_launches counts the launches made.  Agrees with ryd_general_observe within the sum of the two calls'
+ * rounding bounds (other summation order), not bit for bit.
+ * Refused with RYD_ERR_UNSUPPORTED: RYD_OBS_DENSITY and RYD_GENERAL_DENSITY handles; RYD_OBS_ENERGY on a handle with
+ * collapse operators (its generator is H_eff) and on a handle whose generator is not applied by the padded site tables
+ * (CSR terms, ryd_set_path 4096 / 262144, tables beyond the LDS budget - ryd_general_apply_path < 2).  The pair sums
+ * alone work on every ket handle; ryd_general_observe serves the rest, one time per call.  A two-level handle:
+ * RYD_ERR_INVALID (ryd_observe_many).  n_times = 0 returns RYD_OK and touches nothing.
+ * Scratch (one 16-byte time record and tcoef[n_terms] + mvals[E + Dg] per time, a pinned upload buffer and its event)
+ * is the handle's own, grows on demand and is freed by ryd_destroy; the handle's coefficient table, site matrices and
+ * work vector are NOT written, so a solve or ryd_general_observe before or after sees no difference.  If the tables of
+ * all times exceed 256 MiB the times are processed in chunks inside the call: two more launches per extra chunk.
+ * No host synchronisation except while the scratch grows.  One stream per handle, as for ryd_observe_many. */
+int ryd_general_observe_many(ryd_handle* h, const void* states_dev, int32_t n_times, int32_t n_batch,
+                             int64_t stride_t, int64_t stride_b, const double* times, int32_t what,
+                             int32_t local_dim, int32_t n_atoms, int32_t one_digit,
+                             double* out_dev, void* stream);
+
+/* General-path handles: the kernel that the NEXT application of the generator runs with - 0 term by term (k_gen_apply),
+ * 1 the site kernel, 2 the padded site tables (k_gen_apply_fused), 3 the same with the vector in LDS: the value that
+ * ryd_stats.reserved[3] holds after an application, known before the first one.  Builds the handle's site tables if no
+ * call has needed them yet (they depend on the terms and on ryd_set_path only).  ryd_general_observe_many serves the
+ * energy moments when this is 2 or 3. */
+int ryd_general_apply_path(ryd_handle* h, int32_t* path);
 
 /* Replaces: building rho0 = |psi><psi| inside qutip.mesolve for a ket input.
  * psi_dev complex128[batch][2^N] -> rho_dev complex128[batch][2^N][2^N]. */

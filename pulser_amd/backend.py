@@ -123,13 +123,7 @@ class RydState:
 
     def infer_one_state(self) -> str:
         """pulser/backend/state.py: the eigenstate measured as 1."""
-        eig = set(self.eigenstates) - {"x"}  # the leakage state never counts
-        if eig == {"0", "1"}:
-            return "1"
-        for pair, one in _ONE_STATE.items():
-            if set(pair) == eig:
-                return one
-        raise RuntimeError(f"Failed to infer the 'one state' from the eigenstates: {self.eigenstates}")
+        return _infer_one_state(self.eigenstates)
 
     def get_basis_state_from_index(self, index: int) -> str:
         if index < 0:
@@ -238,6 +232,25 @@ class RydState:
                 and np.allclose(np.asarray(self._state), np.asarray(other._state), rtol=0, atol=1e-12))
 
     __hash__ = None  # type: ignore[assignment]
+
+
+def _infer_one_state(eigenstates: Sequence[str]) -> str:
+    """``RydState.infer_one_state`` from the eigenstates alone (no state data)."""
+    eig = set(eigenstates) - {"x"}  # the leakage state never counts
+    if eig == {"0", "1"}:
+        return "1"
+    for pair, one in _ONE_STATE.items():
+        if set(pair) == eig:
+            return one
+    raise RuntimeError(f"Failed to infer the 'one state' from the eigenstates: {tuple(eigenstates)}")
+
+
+def _one_digit(eigenstates: Sequence[str], one_state: str | None) -> int | None:
+    """Index of ``one_state`` (or of the inferred one-state) among the eigenstates, None when it cannot be resolved."""
+    try:
+        return list(eigenstates).index(one_state or _infer_one_state(eigenstates))
+    except (RuntimeError, ValueError):
+        return None
 
 
 class _DeferredRydState(RydState):
@@ -465,13 +478,20 @@ class HamiltonianOperator:
         return {**(seen[digit] if digit is not None else {}), **(energies or {})}
 
     def seed(self, state: RydState, norm2: float, occupation: np.ndarray, correlation: np.ndarray,
-             energy: float | None = None, energy2: float | None = None) -> None:
-        """Hand over what ``Engine.observe_many`` computed for ``state`` at this time (not normalised, local state 0
-        counted): ``observe`` then returns it without a launch and without reading the state."""
+             energy: float | None = None, energy2: float | None = None, digit: int = 0) -> None:
+        """Hand over what ``observe_many`` computed for ``state`` at this time (not normalised, local state ``digit``
+        counted: always 0 on a 2-level Ising engine): ``observe`` then returns it without a launch and without reading
+        the state.  A further call for the same state adds another digit (general engines: one per distinct one-state
+        of the configuration) and keeps the energies of the call that brought them."""
         n2 = float(norm2)
-        energies = None if energy is None else {"energy": float(energy) / n2, "energy2": float(energy2) / n2}
-        self._observed = (id(state), {0: {"occupation": occupation / n2, "correlation": correlation / n2, "digit": 0}},
-                          energies)
+        seen: dict[int, dict[str, Any]] = {}
+        energies = None
+        if self._observed is not None and self._observed[0] == id(state):
+            _, seen, energies = self._observed
+        if energy is not None:
+            energies = {"energy": float(energy) / n2, "energy2": float(energy2) / n2}
+        seen[int(digit)] = {"occupation": occupation / n2, "correlation": correlation / n2, "digit": int(digit)}
+        self._observed = (id(state), seen, energies)
 
     def _h_on(self, arr: np.ndarray) -> np.ndarray:
         """H @ arr for a ket (D,1) or a matrix (D,D) of column vectors."""
@@ -1512,23 +1532,37 @@ def _adopt_pulser_config(config: Any) -> "QutipConfig":
 
 
 def _observe_many_route(states: Sequence[Any], fires: Sequence[bool], engine: Any, n_eigenstates: int,
-                        min_times: int | None) -> tuple[Any, int, list[int]] | None:
-    """Which states of one ``CoherentResults`` a single ``Engine.observe_many`` call serves: (store, sequence of the
+                        min_times: int | None, energy: bool = True) -> tuple[Any, int, list[int]] | None:
+    """Which states of one ``CoherentResults`` a single ``observe_many`` call serves: (store, sequence of the
     store, positions into ``states``), or None when the per-time path serves them all.  A position qualifies when a
     built-in occupation / correlation / energy observable fires there (``fires``) and its state is an unread
-    ``LazyState`` ket of one ``SnapshotStore`` whose tensor ``[times, sequences, 2^N]`` is still on the GPU; the
-    engine must be the 2-level Ising ``Engine`` of one problem in sesolve mode without extra detuning terms, and at
-    least ``min_times`` positions must qualify (None: the path is off).  Everything else - the initial state, states
-    already read, spilled stores, density matrices, general engines - keeps the per-time path."""
-    if min_times is None or engine is None:
+    ``LazyState`` ket of one ``SnapshotStore`` whose tensor ``[times, sequences, dim]`` is still on the GPU, and at
+    least ``min_times`` positions must qualify (None: the path is off).  The engine is the 2-level Ising ``Engine`` of
+    one problem in sesolve mode without extra detuning terms, or a ``GeneralEngine`` (multi-level bases, XY) that
+    ``HamiltonianOperator.observe`` would serve - a ket engine of batch 1 whose ``local_dim`` (2 - 4) is the number of
+    eigenstates and whose dimension is ``local_dim ** n`` - and, when the energy moments are wanted (``energy``), one
+    without collapse operators that applies its generator through the padded site tables
+    (``GeneralEngine.apply_path()``).  Everything else - the initial state, states already read, spilled stores, density
+    matrices - keeps the per-time path."""
+    if min_times is None or engine is None or not hasattr(engine, "observe_many"):
         return None
-    if hasattr(engine, "local_dim") or not hasattr(engine, "observe_many") or n_eigenstates != 2:
-        return None
-    if getattr(engine, "batch", 0) != 1 or getattr(engine, "mode", None) != 0 or getattr(engine, "monte_carlo", False):
-        return None  # (mode 0 = RYD_SESOLVE)
-    dterms = getattr(getattr(engine, "tables", None), "dterms", None)
-    if dterms is not None and len(dterms):
-        return None
+    if hasattr(engine, "local_dim"):
+        d = int(engine.local_dim)
+        if (getattr(engine, "is_density", False) or getattr(engine, "batch", 0) != 1 or not 2 <= d <= 4
+                or d != n_eigenstates or d ** int(engine.n) != engine.dim):
+            return None
+        if energy:
+            apply_path = getattr(engine, "apply_path", None)
+            if getattr(engine, "n_collapse", 0) or apply_path is None or apply_path() not in ("fused", "fused_lds"):
+                return None
+    else:
+        if n_eigenstates != 2:
+            return None
+        if getattr(engine, "batch", 0) != 1 or getattr(engine, "mode", None) != 0 or getattr(engine, "monte_carlo", False):
+            return None  # (mode 0 = RYD_SESOLVE)
+        dterms = getattr(getattr(engine, "tables", None), "dterms", None)
+        if dterms is not None and len(dterms):
+            return None
     store, b, dev = None, 0, None
     positions: list[int] = []
     for pos, (st, f) in enumerate(zip(states, fires)):
@@ -1556,10 +1590,16 @@ class QutipBackendV2:
     config_type: type  # = QutipConfig
     last_timing: dict[str, float] | None = None
     last_observable_engine_stats: dict[str, Any] | None = None
-    # From this many evaluation times on, the occupations, correlations and energy moments of a 2-level Ising ket run
-    # come from ONE Engine.observe_many call over the device snapshots instead of one upload, five launches and one
-    # read-back per time.  None switches that path off.  (Value: profiles/observe_many.md.)
+    # From this many evaluation times on, the occupations, correlations and energy moments of a ket run without
+    # collapse operators come from ONE observe_many call over the device snapshots (Engine.observe_many for 2-level
+    # Ising registers, GeneralEngine.observe_many - one call per distinct one-state - for multi-level bases and XY
+    # mode) instead of one upload, five launches and one read-back per time.  None switches that path off.
+    # (Value: measured for the 2-level route, profiles/observe_many.md.  The general route has NO timing behind it -
+    # profiles/general_observe_many.md says "NOT measured" - and only carries that value over as its floor, below.)
     observe_many_min_times: int | None = 128
+    # The general engines' one-call route never opens below this many times, whatever the threshold above says: the
+    # per-time launch counts of short multi-level / XY runs are part of what the suite pins.
+    _GENERAL_OBSERVE_MANY_FLOOR = 128
 
     def __init__(self, sequence: Any, *, config: QutipConfig | None = None,
                  mimic_qpu: bool = False) -> None:
@@ -1631,6 +1671,7 @@ class QutipBackendV2:
         instance's, so a subclass or an instance may set its own); by default the class attribute."""
         from .engine import Engine, GeneralEngine
         from .general import lower_general
+        from .terms import SUPPORTED_BASES
 
         eigenstates = sim._hamiltonian_data.eigenbasis
         qids = tuple(sim.samples_obj.qubit_ids)
@@ -1638,6 +1679,7 @@ class QutipBackendV2:
         min_times = QutipBackendV2.observe_many_min_times if observe_many_min_times == "class" else observe_many_min_times
         with_leakage = bool(getattr(config.noise_model, "with_leakage", False))
         holder: list[Any] = []  # the engine of the noiseless H(t), built on first use
+        general_one_call = False  # (set below) the one-call observable route of a multi-level / XY run may open
 
         def noiseless_engine() -> Any:
             # qutip_backend.py:259-264: _get_noiseless_hamiltonian(with_leakage) is first
@@ -1651,30 +1693,60 @@ class QutipBackendV2:
                 noiseless["collapse_ops"] = []
                 holder.append(Engine.from_problems([noiseless], mode="sesolve")
                               if sim._fast_path_ok(noiseless)
-                              else GeneralEngine(lower_general(noiseless, mesolve=False)))
+                              # (the one-call route needs the padded site tables of the matrix-free terms; small
+                              # registers are lowered to explicit CSR terms otherwise.  Once the route may open, this
+                              # engine serves the run's per-time calls too - a state somebody has read, a store that
+                              # spilled: their values stay within the bounds, their launch counts are those of the
+                              # padded-table application, not of the CSR engine such a register gets below the threshold)
+                              else GeneralEngine(lower_general(noiseless, mesolve=False,
+                                                               matrix_free=True if general_one_call else None)))
             return holder[0]
 
         wants_energy = any(isinstance(o, (Energy, EnergySecondMoment, EnergyVariance)) for o in config.observables)
 
         pair_or_energy = (Occupation, CorrelationMatrix, Energy, EnergySecondMoment, EnergyVariance)
+        watching = [o for o in config.observables if isinstance(o, pair_or_energy)]
+        hdata = sim._hamiltonian_data
+        # a ket run of the general path: a multi-level basis or XY mode (what _fast_path_ok turns away) without collapse
+        # operators (sesolve).  Master-equation and quantum-jump runs, and every 2-level Ising run, are left exactly as
+        # they are: no option is set and the noiseless engine is lowered as before
+        general_ket_run = (min_times is not None and bool(watching)
+                           and (hdata.basis_name not in SUPPORTED_BASES or len(hdata.eigenbasis) != 2
+                                or hdata.interaction_type == "XY")
+                           and not hdata.collapse_ops()[0])
+        if general_ket_run:
+            # the kets stay on the device (QutipEmulator.run(general_device_snapshots=True)) when enough evaluation times
+            # carry a built-in observable for the one-call path to take them
+            firing = sum(any(o._fires(config, float(t / (T * 1e-3)), T) for o in watching) for t in sim._eval_times_array)
+            if firing >= max(int(min_times), QutipBackendV2._GENERAL_OBSERVE_MANY_FLOOR):
+                options = {**options, "general_device_snapshots": True}
+                general_one_call = True
         many_cache: dict[str, Any] = {}  # the observe_many result of the LAST store seen: shared by the sequences of
         #                                  one batched solve and their repetitions, dropped with the next solve
 
-        def observed_many(rs: Sequence[Any]) -> dict[int, tuple[dict[str, np.ndarray], int, int]]:
-            """position in ``rs`` -> (observe_many result, its row, its column), {} on the per-time path."""
+        def observed_many(rs: Sequence[Any]) -> dict[int, tuple[dict[int, dict[str, np.ndarray]], int, int]]:
+            """position in ``rs`` -> (observe_many results by digit counted, its row, its column), {} on the per-time path."""
             if min_times is None:
                 return {}
             watchers = [o for o in config.observables if isinstance(o, pair_or_energy)]
             if not watchers or not rs:
                 return {}
             fires = [any(o._fires(config, float(r.evaluation_time), T) for o in watchers) for r in rs]
-            route = _observe_many_route([r.state for r in rs], fires, noiseless_engine(), len(eigenstates), min_times)
+            eng = noiseless_engine()
+            need = max(int(min_times), QutipBackendV2._GENERAL_OBSERVE_MANY_FLOOR) if hasattr(eng, "local_dim") else min_times
+            route = _observe_many_route([r.state for r in rs], fires, eng, len(eigenstates), need, wants_energy)
             if route is None:
                 return {}
             store, b, positions = route
+            digits = [0]  # a 2-level Ising engine counts local state 0 and the observables complement
+            if hasattr(eng, "local_dim"):
+                # one call per distinct one-state; an observable whose one-state cannot be resolved keeps the per-time
+                # path.  With none to count (energies only) the inferred one-state rides along: the norm comes with it
+                found = {_one_digit(eigenstates, o.one_state) for o in watchers if isinstance(o, (Occupation, CorrelationMatrix))}
+                digits = sorted(d for d in found if d is not None) or [_one_digit(eigenstates, None) or 0]
             idx = [rs[p].state._i for p in positions]
             times_us = [rs[p].evaluation_time * T / 1000 for p in positions]
-            key = (tuple(idx), tuple(times_us))
+            key = (tuple(idx), tuple(times_us), tuple(digits))
             if many_cache.get("store") is not store or many_cache.get("key") != key:
                 dev = store.device_tensor
                 if dev is None:  # spilled since the route was taken
@@ -1686,9 +1758,13 @@ class QutipBackendV2:
                     import torch
 
                     x = dev[torch.as_tensor(idx, dtype=torch.long, device=dev.device)]
+                if hasattr(eng, "local_dim"):  # (only the first call carries the energy moments)
+                    got = {d: eng.observe_many(x, times_us, one=d, energy=wants_energy and k == 0)
+                           for k, d in enumerate(digits)}
+                else:
+                    got = {0: eng.observe_many(x, times_us, energy=wants_energy)}
                 many_cache.clear()
-                many_cache.update(store=store, key=key,
-                                  got=noiseless_engine().observe_many(x, times_us, energy=wants_energy))
+                many_cache.update(store=store, key=key, got=got)
             got = many_cache["got"]
             return {p: (got, row, b) for row, p in enumerate(positions)}
 
@@ -1705,9 +1781,11 @@ class QutipBackendV2:
                     state = RydState(r.state.unit(), eigenstates=eigenstates)
                 ham = HamiltonianOperator(noiseless_engine(), t * T / 1000, eigenstates, energy_expected=wants_energy)
                 if served is not None:
-                    got, row, b = served
-                    ham.seed(state, got["norm2"][row, b], got["occupation"][row, b], got["correlation"][row, b],
-                             *((got["energy"][row, b], got["energy2"][row, b]) if wants_energy else ()))
+                    by_digit, row, b = served
+                    for k, (d, got) in enumerate(by_digit.items()):
+                        ham.seed(state, got["norm2"][row, b], got["occupation"][row, b], got["correlation"][row, b],
+                                 *((got["energy"][row, b], got["energy2"][row, b]) if wants_energy and k == 0 else ()),
+                                 digit=d)
                 for cb in config.callbacks:
                     cb(config=config, t=float(t), state=state, hamiltonian=ham, result=res)
                 for obs in config.observables:

@@ -185,7 +185,8 @@ struct ryd_handle {
   size_t gen_obs_scratch_bytes = 0;
   bool gen_obs_small_chunks = false;  // test hook: 5 columns per chunk
   // ryd_observe_many: [n_times] ObsManyTime, then the coefficient table [n_times][B][N][4] (grown on demand), and the
-  // pinned host copy of the former with the event that says its last upload has been read
+  // pinned host copy of the former with the event that says its last upload has been read.  ryd_general_observe_many (a
+  // general handle never takes the two-level call): the same record list, then tcoef[n_terms] and mvals[E + Dg] per time
   void* obs_many_dev = nullptr;
   size_t obs_many_bytes = 0;
   ObsManyTime* obs_many_pin = nullptr;

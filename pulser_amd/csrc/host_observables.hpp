@@ -111,7 +111,8 @@ extern "C" int ryd_general_observe(ryd_handle* h, const void* state_dev, double 
   HIPCHK(hipMemsetAsync(out_dev, 0, (size_t)B * stride * sizeof(double), st));
   if (what & (RYD_OBS_OCCUPATION | RYD_OBS_CORRELATION)) {
     hipLaunchKernelGGL(k_gen_obs_pairs, dim3((unsigned)((D + 2047) / 2048), B), dim3(256), 0, st, (const cplx*)state_dev,
-                       (unsigned)D, N, local_dim, one_digit, dm ? 1 : 0, what, out_dev, stride);
+                       (long long)B, B, 0ll, (long long)(dm ? D * D : D), (unsigned)D, N, (int)local_dim, (int)one_digit,
+                       dm ? 1 : 0, (int)what, out_dev, stride);
     HIPCHK(hipGetLastError());
     h->stats.n_launches++;
   }
@@ -243,6 +244,146 @@ extern "C" int ryd_observe_many(ryd_handle* h, const void* states_dev, int32_t n
   return RYD_OK;
 }
 
+// ryd_general_observe for every evaluation time of a run (kets of a general-path handle): k_gen_obs_pairs,
+// k_gen_coefs_fused_many and k_gen_obs_energy_many (k_general.hpp)
+extern "C" int ryd_general_observe_many(ryd_handle* h, const void* states_dev, int32_t n_times, int32_t n_batch,
+                                        int64_t stride_t, int64_t stride_b, const double* times, int32_t what,
+                                        int32_t local_dim, int32_t n_atoms, int32_t one_digit, double* out_dev,
+                                        void* stream) {
+  if (!h) return fail(RYD_ERR_INVALID, "null handle");
+  if (!h->general) return fail(RYD_ERR_INVALID, "general observe_many: not a general-path handle: use ryd_observe_many");
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (local_dim < 2 || local_dim > 4 || n_atoms < 1 || n_atoms > 26 || one_digit < 0 || one_digit >= local_dim)
+    return fail(RYD_ERR_INVALID, "general observe_many: local_dim=%d n_atoms=%d one_digit=%d out of range", local_dim, n_atoms, one_digit);
+  if (h->gen_density)
+    return fail(RYD_ERR_UNSUPPORTED, "general observe_many: kets of a ket handle only; a RYD_GENERAL_DENSITY handle observes vec(rho) with ryd_general_observe");
+  if (what & RYD_OBS_DENSITY)
+    return fail(RYD_ERR_UNSUPPORTED, "general observe_many: RYD_OBS_DENSITY is not served (use ryd_general_observe)");
+  int64_t D = 1;
+  for (int i = 0; i < n_atoms; ++i) {
+    D *= local_dim;
+    if (D > ((int64_t)1 << 26)) return fail(RYD_ERR_INVALID, "general observe_many: %d^%d exceeds 2^26", local_dim, n_atoms);
+  }
+  if ((int64_t)h->dim != D)
+    return fail(RYD_ERR_INVALID, "general observe_many: dim %lld is not %d^%d", (long long)h->dim, local_dim, n_atoms);
+  if (n_times < 0 || n_batch < 1) return fail(RYD_ERR_INVALID, "general observe_many: %d times, batch %d", n_times, n_batch);
+  if (stride_t < D || stride_b < D)
+    return fail(RYD_ERR_INVALID, "general observe_many: strides %lld / %lld are smaller than a ket of %lld amplitudes",
+                (long long)stride_t, (long long)stride_b, (long long)D);
+  const bool energy = (what & RYD_OBS_ENERGY) != 0;
+  if (energy && h->gen_mc_term >= 0)
+    return fail(RYD_ERR_UNSUPPORTED, "general observe_many: energy moments need a handle without collapse operators (its generator is H_eff); ryd_general_observe says the same, ask for the pair sums only");
+  if (n_times == 0) return RYD_OK;
+  if (!states_dev || !times || !out_dev) return fail(RYD_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  hipStream_t st = (hipStream_t)stream;
+  if (energy) {
+    if (!h->gen_sites_valid && (rc = gen_build_sites(h))) return rc;
+    if (!h->gen_fused_ok)
+      return fail(RYD_ERR_UNSUPPORTED, "general observe_many: energy moments need the padded site tables (k_gen_apply_fused); this handle applies its generator another way: use ryd_general_observe per time");
+  }
+  const int N = n_atoms;
+  const int stride = N * N + N + 3;
+  const long long n_states = (long long)n_times * n_batch;
+  HIPCHK(hipMemsetAsync(out_dev, 0, (size_t)n_states * stride * sizeof(double), st));
+  const bool pairs = (what & (RYD_OBS_OCCUPATION | RYD_OBS_CORRELATION)) || !energy;
+  if (pairs) {
+    hipLaunchKernelGGL(k_gen_obs_pairs, dim3((unsigned)((D + 2047) / 2048), (unsigned)std::min<long long>(n_states, 65535)),
+                       dim3(256), 0, st, (const cplx*)states_dev, n_states, (int)n_batch, (long long)stride_t,
+                       (long long)stride_b, (unsigned)D, N, (int)local_dim, (int)one_digit, 0, (int)what, out_dev, stride);
+    HIPCHK(hipGetLastError());
+    h->stats.n_launches++;
+  }
+  if (!energy) return RYD_OK;
+  // (interval, offset) of every time on the host; per time tcoef[n_terms] and mvals[E + Dg] in the handle's scratch (the
+  // handle's own gen_tcoef / gen_fused.mvals / wA are not written).  Calls on one handle are ordered by using ONE stream.
+  const GenFusedDev& F = h->gen_fused;
+  const int n_terms = (int)h->gen_host.size();
+  const size_t per_time = (size_t)(n_terms + F.E + F.Dg);
+  size_t chunk = std::max<size_t>(kGenObsScratchCap / (per_time * sizeof(cplx)), 1);
+  if (h->gen_obs_small_chunks) chunk = std::min<size_t>(chunk, 5);
+  chunk = std::min<size_t>(chunk, (size_t)n_times);
+  const size_t tm_bytes = ((size_t)n_times * sizeof(ObsManyTime) + 255) & ~(size_t)255;
+  const size_t need = tm_bytes + chunk * per_time * sizeof(cplx);
+  if (need > h->obs_many_bytes) {
+    HIPCHK(hipStreamSynchronize(st));  // (an earlier call on this stream may still read the old scratch)
+    if (h->obs_many_dev) HIPCHK(hipFree(h->obs_many_dev));
+    h->obs_many_dev = nullptr;
+    h->obs_many_bytes = 0;
+    HIPCHK(hipMalloc(&h->obs_many_dev, need));
+    h->obs_many_bytes = need;
+  }
+  if (!h->obs_many_ev) HIPCHK(hipEventCreateWithFlags(&h->obs_many_ev, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(h->obs_many_ev));  // the last upload has left the pinned buffer
+  if ((size_t)n_times > h->obs_many_pin_cap) {
+    if (h->obs_many_pin) HIPCHK(hipHostFree(h->obs_many_pin));
+    h->obs_many_pin = nullptr;
+    h->obs_many_pin_cap = 0;
+    HIPCHK(hipHostMalloc((void**)&h->obs_many_pin, (size_t)n_times * sizeof(ObsManyTime), hipHostMallocDefault));
+    h->obs_many_pin_cap = (size_t)n_times;
+  }
+  for (int i = 0; i < n_times; ++i) {
+    const MixPoint m = mix_at(h, times[i]);
+    h->obs_many_pin[i] = {m.u1, m.idx1, 0};
+  }
+  ObsManyTime* tm_dev = (ObsManyTime*)h->obs_many_dev;
+  cplx* table = (cplx*)((char*)h->obs_many_dev + tm_bytes);
+  HIPCHK(hipMemcpyAsync(tm_dev, h->obs_many_pin, (size_t)n_times * sizeof(ObsManyTime), hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(h->obs_many_ev, st));
+  {
+    static bool attr[64] = {};
+    const int dev = h->cfg.device;
+    if (dev < 0 || dev >= 64 || !attr[dev]) {
+      HIPCHK(hipFuncSetAttribute((const void*)k_gen_obs_energy_many<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      HIPCHK(hipFuncSetAttribute((const void*)k_gen_obs_energy_many<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      if (dev >= 0 && dev < 64) attr[dev] = true;
+    }
+  }
+  GenObsManyArgs A;
+  A.terms = h->gen_terms_dev;
+  A.diag_terms = h->gen_diag_terms_dev;
+  for (int k = 0; k < 4; ++k) {
+    const bool have = k < h->gen_n_diag;
+    A.diag_idx[k] = have ? h->gen_diag_host[k] : 0;
+    A.diag_val[k] = have ? h->gen_host[h->gen_diag_host[k]].dev.val : nullptr;
+  }
+  A.F = F;
+  A.stride_t = stride_t;
+  A.stride_b = stride_b;
+  A.dim = (long long)D;
+  A.n_batch = n_batch;
+  A.n_terms = n_terms;
+  A.n_diag = h->gen_n_diag;
+  A.d = h->gen_d;
+  A.n_dig = h->gen_ndig;
+  A.with_norm = pairs ? 0 : 1;
+  A.out_stride = stride;
+  A.off = N * N + N + 1;
+  A.norm_off = N;
+  A.table = table;
+  // the application's LDS image and a second buffer for the waves' partial sums (<= 150 KiB + 8 KiB of the CU's 160)
+  const size_t lds = h->gen_fused_lds + 4 * GEN_FUSED_ROWS * 2 * sizeof(cplx);
+  const unsigned n_rb = (unsigned)((D + GEN_FUSED_ROWS - 1) / GEN_FUSED_ROWS);
+  const unsigned gx = (n_rb + GEN_OBS_ROW_BLOCKS - 1) / GEN_OBS_ROW_BLOCKS;
+  for (size_t t0 = 0; t0 < (size_t)n_times; t0 += chunk) {  // (one chunk unless the tables exceed kGenObsScratchCap)
+    const size_t nt = std::min<size_t>(chunk, (size_t)n_times - t0);
+    hipLaunchKernelGGL(k_gen_coefs_fused_many, dim3((unsigned)nt), dim3(256), 0, st, (const cplx*)h->pp_dev, h->n_knots - 1,
+                       (const int*)h->gen_series_dev, (const int*)h->gen_conj_dev, (const cplx*)h->gen_scale_dev, n_terms,
+                       (const ObsManyTime*)(tm_dev + t0), table, F);
+    HIPCHK(hipGetLastError());
+    A.states = (const cplx*)states_dev + (long long)t0 * stride_t;
+    A.n_states = (long long)nt * n_batch;
+    A.out = out_dev + t0 * (size_t)n_batch * stride;
+    const dim3 grid(gx, (unsigned)std::min<long long>(A.n_states, 65535));
+    if (h->gen_fused_xlds) hipLaunchKernelGGL(k_gen_obs_energy_many<true>, grid, dim3(256), lds, st, A);
+    else hipLaunchKernelGGL(k_gen_obs_energy_many<false>, grid, dim3(256), lds, st, A);
+    HIPCHK(hipGetLastError());
+    h->stats.n_launches += 2;
+  }
+  return RYD_OK;
+}
+
 extern "C" int ryd_ket_to_dm(ryd_handle* h, const void* psi_dev, void* rho_dev, void* stream) {
   if (!h || !psi_dev || !rho_dev) return fail(RYD_ERR_INVALID, "null argument");
   if (h->general) return fail(RYD_ERR_INVALID, "not available on a general-path handle");
@@ -350,6 +491,21 @@ extern "C" int ryd_get_stats(const ryd_handle* h, ryd_stats* out) {
   if (!h || !out) return fail(RYD_ERR_INVALID, "null argument");
   *out = h->stats;
   if (hermitian_path(h)) out->passes = 2;  // row pass + symmetrisation
+  return RYD_OK;
+}
+
+// The kernel that the NEXT application of a general handle's generator runs with, from its site tables (a function of the
+// terms and of ryd_set_path; built here if no call has needed them yet): what ryd_stats.reserved[3] reports after an
+// application, asked before the first one - ryd_general_observe_many serves the energy moments of 2 and 3 only.
+extern "C" int ryd_general_apply_path(ryd_handle* h, int32_t* path) {
+  if (!h || !path) return fail(RYD_ERR_INVALID, "null argument");
+  if (!h->general || h->gen_host.empty()) return fail(RYD_ERR_INVALID, "ryd_general_apply_path needs a general-path handle");
+  if (!h->gen_sites_valid) {
+    HIPCHK(hipSetDevice(h->cfg.device));
+    int rc = gen_build_sites(h);
+    if (rc) return rc;
+  }
+  *path = h->gen_fused_ok ? (h->gen_fused_xlds ? 3 : 2) : h->gen_sites_ok ? 1 : 0;
   return RYD_OK;
 }
 

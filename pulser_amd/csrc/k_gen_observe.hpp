@@ -27,31 +27,40 @@ __device__ __forceinline__ unsigned gen_obs_word(unsigned idx, int d, int N, uns
   return w;
 }
 
-// out[b] = the row of k_obs_pairs for state b.  One block stages a chunk of probabilities in LDS and, beside each, the
-// digit word of its index (computed once per element), then takes the pair sums of k_observe.hpp on the words.
-// is_dm: `st` is [batch][D][D] (a density matrix, or vec(rho) of a RYD_GENERAL_DENSITY handle) and p_i = Re rho_ii.
-// N <= 26 (d^N <= 2^26).
-__global__ __launch_bounds__(256) void k_gen_obs_pairs(const cplx* __restrict__ st, unsigned D, int N, int d, int one,
-                                                       int is_dm, int what, double* __restrict__ out, int out_stride) {
+// out[s] = the row of k_obs_pairs for state s = it * n_batch + b at states + it * stride_t + b * stride_b (64-bit
+// offsets), the states taken from the second grid axis with a stride (it is capped at 65 535 workgroups), exactly as
+// k_obs_pairs addresses them: ryd_general_observe passes n_states = n_batch = its batch, ryd_general_observe_many every
+// evaluation time of a run.  One block stages a chunk of probabilities in LDS and, beside each, the digit word of its
+// index (computed once per block: it does not depend on the state), then takes the pair sums of k_observe.hpp on the words.
+// is_dm: a state is [D][D] (a density matrix, or vec(rho) of a RYD_GENERAL_DENSITY handle; stride_b = D * D) and
+// p_i = Re rho_ii.  N <= 26 (d^N <= 2^26).
+__global__ __launch_bounds__(256) void k_gen_obs_pairs(const cplx* __restrict__ states, long long n_states, int n_batch,
+                                                       long long stride_t, long long stride_b, unsigned D, int N, int d,
+                                                       int one, int is_dm, int what, double* __restrict__ out,
+                                                       int out_stride) {
   __shared__ double ps[kObsCH];
   __shared__ unsigned wd[kObsCH];
-  const int b = blockIdx.y;
   const size_t base = (size_t)blockIdx.x * kObsCH;
-  const cplx* __restrict__ sb = st + (size_t)b * D * (is_dm ? (size_t)D : 1);
   for (int i = threadIdx.x; i < kObsCH; i += blockDim.x) {
     const size_t g = base + i;
-    double p = 0.0;
-    unsigned w = 0;
-    if (g < D) {
-      if (is_dm) p = sb[g * D + g].x;
-      else { const cplx v = sb[g]; p = v.x * v.x + v.y * v.y; }
-      w = gen_obs_word((unsigned)g, d, N, (unsigned)one);
-    }
-    ps[i] = p;
-    wd[i] = w;
+    wd[i] = g < D ? gen_obs_word((unsigned)g, d, N, (unsigned)one) : 0u;
   }
-  __syncthreads();
-  obs_pair_sums<true>(ps, wd, base, N, what, out + (size_t)b * out_stride);
+  for (long long s = blockIdx.y; s < n_states; s += gridDim.y) {
+    const long long it = s / n_batch, b = s - it * n_batch;
+    const cplx* __restrict__ sb = states + it * stride_t + b * stride_b;
+    for (int i = threadIdx.x; i < kObsCH; i += blockDim.x) {
+      const size_t g = base + i;
+      double p = 0.0;
+      if (g < D) {
+        if (is_dm) p = sb[g * D + g].x;
+        else { const cplx v = sb[g]; p = v.x * v.x + v.y * v.y; }
+      }
+      ps[i] = p;
+    }
+    __syncthreads();
+    obs_pair_sums<true>(ps, wd, base, N, what, out + (size_t)s * out_stride);
+    __syncthreads();  // `ps` is filled again for the next state of this workgroup
+  }
 }
 
 // X[b * nc + j][a] = rho[b][a][c0 + j] for j < nc: columns c0 .. c0 + nc of every D x D matrix as contiguous vectors,

@@ -216,13 +216,14 @@ struct GenFusedDev {
   int gK[GEN_FUSED_MAX_GROUPS], gBegin[GEN_FUSED_MAX_GROUPS], gEnd[GEN_FUSED_MAX_GROUPS];
 };
 
-// tcoef[t] (as k_gen_coefs) and then the site-matrix entries, one workgroup
-__global__ __launch_bounds__(256) void k_gen_coefs_fused(const cplx* __restrict__ pp, int n_int, const int* __restrict__ series,
-                                                         const int* __restrict__ conjf, const cplx* __restrict__ scale,
-                                                         int n_terms, int idx, double u1, double w1, double u2, double w2,
-                                                         cplx* __restrict__ tcoef, const GenFusedDev F) {
-  __shared__ double tc_raw[2 * 96];  // MAX_GEN_TERMS coefficients
-  cplx* tc = reinterpret_cast<cplx*>(tc_raw);
+// tcoef[t] (as k_gen_coefs) and then the site-matrix entries, by one workgroup: the body of k_gen_coefs_fused (one
+// exponential, into the handle's tables) and of k_gen_coefs_fused_many (one evaluation time per workgroup, into the
+// scratch of ryd_general_observe_many) - one function, so the two cannot drift.  `tc`: [MAX_GEN_TERMS] in LDS.
+__device__ __forceinline__ void gen_coefs_fused_body(const cplx* __restrict__ pp, int n_int, const int* __restrict__ series,
+                                                     const int* __restrict__ conjf, const cplx* __restrict__ scale,
+                                                     int n_terms, int idx, double u1, double w1, double u2, double w2,
+                                                     cplx* __restrict__ tcoef, const GenFusedDev& F, cplx* __restrict__ mvals,
+                                                     cplx* tc) {
   for (int t = threadIdx.x; t < n_terms; t += blockDim.x) {
     cplx v = make_double2(w1 + w2, 0.0);
     if (series[t] >= 0) {
@@ -239,8 +240,30 @@ __global__ __launch_bounds__(256) void k_gen_coefs_fused(const cplx* __restrict_
   for (int p = threadIdx.x; p < P; p += blockDim.x) {
     cplx m = make_double2(0.0, 0.0);
     for (int k = F.contrib_start[p]; k < F.contrib_start[p + 1]; ++k) m = cfma(tc[F.contrib_term[k]], F.contrib_val[k], m);
-    F.mvals[p] = m;
+    mvals[p] = m;
   }
+}
+
+__global__ __launch_bounds__(256) void k_gen_coefs_fused(const cplx* __restrict__ pp, int n_int, const int* __restrict__ series,
+                                                         const int* __restrict__ conjf, const cplx* __restrict__ scale,
+                                                         int n_terms, int idx, double u1, double w1, double u2, double w2,
+                                                         cplx* __restrict__ tcoef, const GenFusedDev F) {
+  __shared__ double tc_raw[2 * 96];  // MAX_GEN_TERMS coefficients
+  gen_coefs_fused_body(pp, n_int, series, conjf, scale, n_terms, idx, u1, w1, u2, w2, tcoef, F, F.mvals,
+                       reinterpret_cast<cplx*>(tc_raw));
+}
+
+// Workgroup i: the tables of evaluation time i at one time with weight 1 (w1 = 1, w2 = 0, as ryd_general_observe asks
+// k_gen_coefs_fused for them) into table[i] = tcoef[n_terms], mvals[E + Dg]; nothing of the handle is written.
+__global__ __launch_bounds__(256) void k_gen_coefs_fused_many(const cplx* __restrict__ pp, int n_int, const int* __restrict__ series,
+                                                              const int* __restrict__ conjf, const cplx* __restrict__ scale,
+                                                              int n_terms, const ObsManyTime* __restrict__ tm,
+                                                              cplx* __restrict__ table, const GenFusedDev F) {
+  __shared__ double tc_raw[2 * 96];
+  const ObsManyTime t = tm[blockIdx.x];
+  cplx* row = table + (size_t)blockIdx.x * (size_t)(n_terms + F.E + F.Dg);
+  gen_coefs_fused_body(pp, n_int, series, conjf, scale, n_terms, t.idx, t.u, 1.0, t.u, 0.0, row, F, row + n_terms,
+                       reinterpret_cast<cplx*>(tc_raw));
 }
 
 struct GenFusedArgs {
@@ -305,6 +328,31 @@ __device__ __forceinline__ void gen_fused_sites(const GenSiteF* __restrict__ sit
   }
 }
 
+// Every site group of one row for this wave: acc += off-diagonal entries x gathered amplitudes, dsum += site diagonals
+// (k_gen_apply_fused, and k_gen_obs_energy_many for the same value of the row)
+__device__ __forceinline__ void gen_fused_row(const GenFusedDev& F, int wave, const cplx* __restrict__ mv,
+                                              const cplx* __restrict__ mvd, const int* __restrict__ dl,
+                                              const cplx* __restrict__ x, int row, unsigned long long digits, unsigned mask,
+                                              cplx& acc, cplx& dsum) {
+  const GenSiteF* __restrict__ sites = F.sites;
+  for (int g = 0; g < F.n_groups; ++g) {
+    const int K = F.gK[g], s0 = F.gBegin[g], s1 = F.gEnd[g];
+    switch (K) {
+      case 0: for (int s = s0 + wave; s < s1; s += 4) {  // diagonal-only sites
+                const GenSiteF si = sites[s];
+                const int R = (int)((digits >> si.shift0) & mask) * si.mul + (int)((digits >> si.shift1) & (unsigned)si.mask1);
+                const cplx dg = mvd[si.diag_off + R];
+                dsum.x += dg.x; dsum.y += dg.y;
+              } break;
+      case 1: gen_fused_sites<1>(sites, s0, s1, wave, mv, mvd, dl, x, row, digits, mask, K, acc, dsum); break;
+      case 2: gen_fused_sites<2>(sites, s0, s1, wave, mv, mvd, dl, x, row, digits, mask, K, acc, dsum); break;
+      case 3: gen_fused_sites<3>(sites, s0, s1, wave, mv, mvd, dl, x, row, digits, mask, K, acc, dsum); break;
+      case 4: gen_fused_sites<4>(sites, s0, s1, wave, mv, mvd, dl, x, row, digits, mask, K, acc, dsum); break;
+      default: gen_fused_sites<0>(sites, s0, s1, wave, mv, mvd, dl, x, row, digits, mask, K, acc, dsum); break;
+    }
+  }
+}
+
 #define GEN_FUSED_ROWS 64
 template <bool XLDS>
 __global__ __launch_bounds__(256) void k_gen_apply_fused(const GenFusedArgs A) {
@@ -359,23 +407,7 @@ __global__ __launch_bounds__(256) void k_gen_apply_fused(const GenFusedArgs A) {
     const cplx* __restrict__ x = XLDS ? xs : xg;
     const unsigned long long digits = gen_pack_digits(row, A.d, A.n_dig);
     const unsigned mask = A.d <= 4 ? 3u : 15u;
-    const GenSiteF* __restrict__ sites = A.F.sites;
-    for (int g = 0; g < A.F.n_groups; ++g) {
-      const int K = A.F.gK[g], s0 = A.F.gBegin[g], s1 = A.F.gEnd[g];
-      switch (K) {
-        case 0: for (int s = s0 + wave; s < s1; s += 4) {  // diagonal-only sites
-                  const GenSiteF si = sites[s];
-                  const int R = (int)((digits >> si.shift0) & mask) * si.mul + (int)((digits >> si.shift1) & (unsigned)si.mask1);
-                  const cplx dg = mvd[si.diag_off + R];
-                  dsum.x += dg.x; dsum.y += dg.y;
-                } break;
-        case 1: gen_fused_sites<1>(sites, s0, s1, wave, mv, mvd, dl, x, (int)row, digits, mask, K, acc, dsum); break;
-        case 2: gen_fused_sites<2>(sites, s0, s1, wave, mv, mvd, dl, x, (int)row, digits, mask, K, acc, dsum); break;
-        case 3: gen_fused_sites<3>(sites, s0, s1, wave, mv, mvd, dl, x, (int)row, digits, mask, K, acc, dsum); break;
-        case 4: gen_fused_sites<4>(sites, s0, s1, wave, mv, mvd, dl, x, (int)row, digits, mask, K, acc, dsum); break;
-        default: gen_fused_sites<0>(sites, s0, s1, wave, mv, mvd, dl, x, (int)row, digits, mask, K, acc, dsum); break;
-      }
-    }
+    gen_fused_row(A.F, wave, mv, mvd, dl, x, (int)row, digits, mask, acc, dsum);
   }
   if (wave != 0) {
     red[(wave * GEN_FUSED_ROWS + lane) * 2] = acc;
@@ -397,6 +429,135 @@ __global__ __launch_bounds__(256) void k_gen_apply_fused(const GenFusedArgs A) {
     r.y += bb.y;
   }
   A.out[boff + row] = r;
+}
+
+// ---------------------------------------------------------------------------
+// ryd_general_observe_many: <H> and <H^2> of the kets of EVERY evaluation time of a run, w = -i H x never written.
+// ---------------------------------------------------------------------------
+// k_gen_apply_fused with the reduction of k_obs_energy in place of its store.  State s = it * n_batch + b lives at
+// states + it * stride_t + b * stride_b (64-bit offsets) and is applied with the tables of time `it`
+// (k_gen_coefs_fused_many: table[it] = tcoef[n_terms], mvals[E + Dg]).  A workgroup stages the site matrices of the time
+// (and, XLDS, the whole ket) in LDS ONCE and then walks GEN_OBS_ROW_BLOCKS blocks of 64 rows with them: re-staging a
+// 64-KiB ket for every 64 rows, as one application launch does, would read it from L2 64 times per state here.  Per
+// row block the four waves split the sites exactly as in the application (gen_fused_row, same order of every sum), so
+// wave 0 holds the application's own w_r; it keeps -Im(conj(x_r) w_r), |w_r|^2 (and |x_r|^2 when no pair launch ran)
+// in registers across its row blocks, reduces them with __shfl_down and issues one fp64 atomicAdd per sum, workgroup
+// and state.  The waves' partial sums alternate between two LDS buffers, so a row block costs one barrier.  The row
+// offsets `delta` do not depend on the time: staged once per workgroup.  The second grid axis is the state, capped at
+// 65 535: the kernel strides over s.
+#define GEN_OBS_ROW_BLOCKS 8
+struct GenObsManyArgs {
+  const cplx* states;
+  const cplx* table;         // [n_times][n_terms + E + Dg]
+  const GenTermDev* terms;   // only the diagonal (kind 2) terms are read here
+  const int* diag_terms;
+  const cplx* diag_val[4];   // as GenFusedArgs
+  int diag_idx[4];
+  GenFusedDev F;
+  long long n_states, stride_t, stride_b, dim;
+  int n_batch, n_terms, n_diag, d, n_dig;
+  int with_norm;             // also out[s][norm_off] += sum |x_r|^2
+  double* out;               // [n_states][out_stride]
+  int out_stride, off, norm_off;
+};
+
+template <bool XLDS>
+__global__ __launch_bounds__(256) void k_gen_obs_energy_many(const GenObsManyArgs A) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int E = A.F.E, Dg = A.F.Dg;
+  cplx* mv = reinterpret_cast<cplx*>(smem);                              // [E] off-diagonal, [Dg] diagonal
+  cplx* mvd = mv + E;
+  cplx* red = mvd + Dg;                                                  // [2][4][64][2]: partial sums, two buffers
+  int* dl = reinterpret_cast<int*>(red + 2 * 4 * GEN_FUSED_ROWS * 2);    // [E]
+  cplx* xs = reinterpret_cast<cplx*>(dl + ((E + 3) & ~3));               // [dim] (XLDS)
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int n_rb = (int)((A.dim + GEN_FUSED_ROWS - 1) / GEN_FUSED_ROWS);
+  const int rb0 = blockIdx.x * GEN_OBS_ROW_BLOCKS;
+  const int rb1 = rb0 + GEN_OBS_ROW_BLOCKS < n_rb ? rb0 + GEN_OBS_ROW_BLOCKS : n_rb;
+  const unsigned mask = A.d <= 4 ? 3u : 15u;
+  const int per_time = A.n_terms + E + Dg;
+  for (int i = threadIdx.x; i < E; i += 256) dl[i] = A.F.delta[i];
+  for (long long s = blockIdx.y; s < A.n_states; s += gridDim.y) {
+    const long long it = s / A.n_batch, b = s - it * A.n_batch;
+    const cplx* __restrict__ xg = A.states + it * A.stride_t + b * A.stride_b;
+    const cplx* __restrict__ tc = A.table + (size_t)it * per_time;
+    const cplx* __restrict__ mg = tc + A.n_terms;
+    for (int i = threadIdx.x; i < E + Dg; i += 256) mv[i] = mg[i];
+    if (XLDS) {
+      // the whole vector into LDS, eight independent 16-byte loads per lane in flight
+      const int n = (int)A.dim;
+      for (int b0 = threadIdx.x; b0 < n; b0 += 256 * 8) {
+        cplx r[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int i = b0 + u * 256;
+          r[u] = i < n ? xg[i] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int i = b0 + u * 256;
+          if (i < n) xs[i] = r[u];
+        }
+      }
+    }
+    __syncthreads();
+    const cplx* __restrict__ x = XLDS ? xs : xg;
+    double e1 = 0.0, e2 = 0.0, nrm = 0.0;
+    for (int rb = rb0; rb < rb1; ++rb) {
+      const long long row = (long long)rb * GEN_FUSED_ROWS + lane;
+      const bool live = row < A.dim;
+      cplx* rbuf = red + (rb & 1) * (4 * GEN_FUSED_ROWS * 2);
+      cplx xr = make_double2(0.0, 0.0), dsum = make_double2(0.0, 0.0), acc = make_double2(0.0, 0.0);
+      if (live) {
+        if (wave == 0) {  // the row's own amplitude and the dense diagonal terms, in the application's order
+          xr = x[row];
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (k < A.n_diag) dsum = cfma(tc[A.diag_idx[k]], A.diag_val[k][row], dsum);
+          for (int k = 4; k < A.n_diag; ++k) {
+            const int t = A.diag_terms[k];
+            dsum = cfma(tc[t], A.terms[t].val[row], dsum);
+          }
+        }
+        const unsigned long long digits = gen_pack_digits(row, A.d, A.n_dig);
+        gen_fused_row(A.F, wave, mv, mvd, dl, x, (int)row, digits, mask, acc, dsum);
+      }
+      if (wave != 0) {
+        rbuf[(wave * GEN_FUSED_ROWS + lane) * 2] = acc;
+        rbuf[(wave * GEN_FUSED_ROWS + lane) * 2 + 1] = dsum;
+      }
+      __syncthreads();
+      if (wave == 0 && live) {
+#pragma unroll
+        for (int w = 1; w < 4; ++w) {
+          const cplx a = rbuf[(w * GEN_FUSED_ROWS + lane) * 2], dd = rbuf[(w * GEN_FUSED_ROWS + lane) * 2 + 1];
+          acc.x += a.x; acc.y += a.y;
+          dsum.x += dd.x; dsum.y += dd.y;
+        }
+        acc = cfma(dsum, xr, acc);  // w_r = (-i H x)_r
+        e1 -= xr.x * acc.y - xr.y * acc.x;
+        e2 = fma(acc.x, acc.x, fma(acc.y, acc.y, e2));
+        nrm = fma(xr.x, xr.x, fma(xr.y, xr.y, nrm));
+      }
+    }
+    if (wave == 0) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        e1 += __shfl_down(e1, o, 64);
+        e2 += __shfl_down(e2, o, 64);
+        nrm += __shfl_down(nrm, o, 64);
+      }
+      if (lane == 0) {
+        double* o = A.out + (size_t)s * A.out_stride;
+        atomicAdd(o + A.off, e1);
+        atomicAdd(o + A.off + 1, e2);
+        if (A.with_norm) atomicAdd(o + A.norm_off, nrm);
+      }
+    }
+    // (every wave has passed the last row block's barrier after its last read of `mv` and `xs`: they may be staged again;
+    // the partial sums wave 0 may still be reading are not touched before the next staging barrier)
+  }
 }
 
 #define MAX_GEN_TERMS 96

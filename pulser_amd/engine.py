@@ -900,6 +900,46 @@ class GeneralEngine:
                                                 out.data_ptr(), self._stream()))
         return _obs_unpack(out, n)
 
+    def observe_many(self, states: Any, times: Any, one: int = 0, occupation: bool = True, correlation: bool = True,
+                     energy: bool = True) -> dict[str, np.ndarray]:
+        """``ryd_general_observe_many``: what :meth:`observe` returns, for the kets of every evaluation time of a run in
+        one device call (a memset and at most three launches) and one device-to-host copy.  ``states`` is a complex128
+        tensor ``[T, B, dim]`` on this engine's device, or any view of one whose last axis is contiguous: the strides of
+        the first two axes are passed on, so ``dev[:, b:b + 1]`` of a snapshot tensor is observed in place.  ``times``
+        [T] (us) need not be sorted or distinct.  ``B`` is anything: the engine's one problem serves every entry.  Ket
+        engines only; the energy moments need the padded-table application (:meth:`apply_path` ``fused`` /
+        ``fused_lds``) and an engine without collapse operators - :meth:`observe` serves the rest, one time per call.
+        Returns host arrays ``norm2`` [T, B], ``occupation`` [T, B, N], ``correlation`` [T, B, N, N], ``energy``
+        [T, B], ``energy2`` [T, B] - NOT normalised (divide by ``norm2``); what was not asked for is 0."""
+        torch = self.torch
+        one = int(one)
+        if not 0 <= one < self.local_dim:
+            raise ValueError(f"'one' must be a digit in [0, {self.local_dim}), got {one}")
+        if not 2 <= self.local_dim <= 4:
+            raise ValueError(f"observe_many takes local dimensions 2 - 4, got {self.local_dim}")
+        if not (isinstance(states, torch.Tensor) and states.is_cuda and states.device == self.device):
+            raise ValueError(f"states must be a torch tensor on {self.device}")
+        if states.dtype != torch.complex128:
+            raise ValueError(f"states must be complex128, got {states.dtype}")
+        if states.dim() != 3 or int(states.shape[2]) != self.dim or int(states.shape[1]) < 1:
+            raise ValueError(f"states must have the shape [T, B >= 1, {self.dim}], got {tuple(states.shape)}")
+        if states.stride(2) != 1:
+            raise ValueError("the last axis of states must be contiguous (the first two may be strided)")
+        n_t, n_b = int(states.shape[0]), int(states.shape[1])
+        tt = np.ascontiguousarray(times, dtype=np.float64)
+        if tt.shape != (n_t,):
+            raise ValueError(f"need one time per state of the first axis ({n_t}), got {tt.shape}")
+        # (the stride of an axis of length 1 is arbitrary in torch and never used: any valid value will do)
+        stride_b = int(states.stride(1)) if n_b > 1 else self.dim
+        stride_t = int(states.stride(0)) if n_t > 1 else max(n_b * stride_b, self.dim)
+        n = self.n
+        what = _obs_what(occupation, correlation, energy)
+        out = torch.empty((n_t, n_b, n * n + n + 3), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.ryd_general_observe_many(self._h, states.data_ptr(), n_t, n_b, stride_t, stride_b,
+                                                     tt.ctypes.data, what, self.local_dim, n, one, out.data_ptr(),
+                                                     self._stream()))
+        return _obs_unpack(out, n)
+
     def set_path(self, force_multi_launch: bool, no_sites: bool = False, no_fused: bool = False,
                  observe_small_chunks: bool = False) -> None:
         """Test hook: one launch per Taylor stage instead of the persistent
@@ -909,6 +949,16 @@ class GeneralEngine:
         :meth:`observe` of density matrices takes 5 columns per chunk (the chunked path on a small state)."""
         _lib.check(self.lib.ryd_set_path(self._h, int(bool(force_multi_launch)) | (4096 if no_sites else 0)
                                          | (262144 if no_fused else 0) | (524288 if observe_small_chunks else 0)))
+
+    def reset_stats(self) -> None:
+        _lib.check(self.lib.ryd_reset_stats(self._h))
+
+    def apply_path(self) -> str:
+        """The kernel that the next application of the generator runs with (``ryd_general_apply_path``): what
+        ``stats()["apply_path"]`` says after an application, known before the first one."""
+        path = C.c_int32(0)
+        _lib.check(self.lib.ryd_general_apply_path(self._h, C.byref(path)))
+        return ("terms", "sites", "fused", "fused_lds")[path.value]
 
     def stats(self) -> dict[str, Any]:
         s = RydStats()

@@ -940,7 +940,7 @@ class QutipEmulator:
     _DEVICE_STATE_BYTES = 1 << 30
 
     @staticmethod
-    def _check_snapshot_budget(n_snapshots: int, state_bytes: int) -> None:
+    def _check_snapshot_budget(n_snapshots: int, state_bytes: int, what: str = "density matrix") -> None:
         """Refuse evaluation-time lists whose stored states cannot fit the device (the reference
         would fail the same way in host memory, after hours): the solver needs 4 work copies, the
         results one copy per evaluation time."""
@@ -951,7 +951,7 @@ class QutipEmulator:
         if need > 0.9 * free:
             raise MemoryError(
                 f"Storing the state at {n_snapshots} evaluation times needs {need / 2**30:.0f} GiB of "
-                f"device memory ({state_bytes / 2**30:.2f} GiB per density matrix, {free / 2**30:.0f} GiB "
+                f"device memory ({state_bytes / 2**30:.2f} GiB per {what}, {free / 2**30:.0f} GiB "
                 "free): use evaluation_times='Minimal' or a short list of times instead of 'Full'."
             )
 
@@ -1044,32 +1044,47 @@ class QutipEmulator:
         n = self._hamiltonian_data.n_qudits
         out = []
         kw = self._engine_kwargs(options, general=True)
-        solved: list[tuple[np.ndarray, np.ndarray]] = []
+        # ``general_device_snapshots`` (sesolve kets): the solved tensor stays in HBM behind a SnapshotStore, one per
+        # trajectory, and the results hold LazyState objects - what the 2-level path always does
+        keep = bool(options.get("general_device_snapshots")) and mode == "sesolve"
+        solved: list[tuple[np.ndarray, Any]] = []
         engines = [GeneralEngine(lower_general(prob, mesolve=(mode == "mesolve"))) for prob in problems]
         try:
+            if keep:
+                # every trajectory's snapshot tensor is on the device at once (the stores are built after the last
+                # solve), next to each engine's work vectors: the budget counts the kets of ALL trajectories per time
+                self._check_snapshot_budget(len(times) - 1, 16 * sum(eng.dim for eng in engines),
+                                            "evaluation time (the kets of all trajectories)")
             states = [eng.new_state(np.asarray(self._initial_state).reshape(-1)) for eng in engines]
             firsts = [st.cpu().numpy()[0] for st in states]
             if len(engines) > 1 and all(eng.dim <= 4096 for eng in engines) and np.all(np.diff(times) > 0):
                 # the trajectories of a multi-level / XY run: one launch, one workgroup per trajectory
                 snaps = GeneralEngine.solve_many(engines, states, times, **kw)
-                solved = [(f, s.cpu().numpy()) for f, s in zip(firsts, snaps)]
+                solved = [(f, s if keep else s.cpu().numpy()) for f, s in zip(firsts, snaps)]
                 self.last_engine_stats = engines[0].stats()
             else:
                 for eng, st, f in zip(engines, states, firsts):
-                    solved.append((f, eng.solve(st, times, **kw).cpu().numpy()))
+                    snap = eng.solve(st, times, **kw)
+                    solved.append((f, snap if keep else snap.cpu().numpy()))
                     self.last_engine_stats = eng.stats()
         finally:
             for eng in engines:
                 eng.close()
         for prob, (first, host) in zip(problems, solved):
             D = len(prob["eigenbasis"]) ** n
+            store = SnapshotStore(host) if keep else None
             results = []
             for i, t in enumerate(times):
-                st = first if i == 0 else host[i - 1][0]
-                if mode == "mesolve":
-                    st = st.reshape(D, D)
+                st: Any
+                if keep:
+                    st = QState(first) if i == 0 else LazyState(store, i - 1, 0, (D, 1))
+                else:
+                    st = first if i == 0 else host[i - 1][0]
+                    if mode == "mesolve":
+                        st = st.reshape(D, D)
+                    st = QState(st)
                 results.append(
-                    StateResult(qids, self._meas_basis, QState(st),
+                    StateResult(qids, self._meas_basis, st,
                                 self._meas_basis in self.basis_name,
                                 evaluation_time=float(t / (self._tot_duration * 1e-3))))
             out.append(CoherentResults(results, n, self.basis_name, times, self._meas_basis,
@@ -1169,7 +1184,11 @@ class QutipEmulator:
         (3- / 4-level bases, XY mode, collapse operators whose ``sum C^dag C`` is not diagonal) run as
         quantum-jump trajectories on the general path - kets of d^N amplitudes, so registers beyond the
         master equation's 2^26-entry Liouvillian (XY up to 26 atoms, 3 levels up to 16) - instead of the
-        default master-equation fallback.  Seeds follow ``seeds=`` exactly as on the 2-level path."""
+        default master-equation fallback.  Seeds follow ``seeds=`` exactly as on the 2-level path.
+
+        ``general_device_snapshots=True``: the kets of a multi-level / XY run without collapse operators stay on the
+        GPU (one ``SnapshotStore`` per trajectory) and ``results.states`` holds ``LazyState`` objects that cross PCIe
+        when they are read, as the states of a 2-level run do; by default they are host ``QState`` objects."""
         warnings.warn(
             "QutipEmulator is deprecated as of pulser 1.9. Please use QutipBackendV2 instead.",
             DeprecationWarning,
