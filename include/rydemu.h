@@ -433,6 +433,36 @@ int ryd_observe_many(ryd_handle* h, const void* states_dev, int32_t n_times, int
                      int64_t stride_t, int64_t stride_b, const double* times, int32_t what,
                      double* out_dev, void* stream);
 
+/* ryd_observe + RYD_OBS_DENSITY for every density matrix of a master-equation run in one call: one memset and at most
+ * three launches for any n_times, n_batch and `what`, instead of one download, host normalisation, upload, four
+ * launches and one read-back per evaluation time.  A separate entry point: ryd_observe_many keeps refusing density
+ * matrices and RYD_MESOLVE handles.
+ *   handle      a two-level RYD_SESOLVE handle without collapse operators (the V2 backend's noiseless engine: H(t) is
+ *               the noiseless one, as with ryd_observe + RYD_OBS_DENSITY) or a RYD_MESOLVE handle.  Monte-Carlo handles
+ *               and handles with extra detuning terms: RYD_ERR_UNSUPPORTED (ryd_observe serves them, one state per
+ *               call); a general-path handle: RYD_ERR_INVALID; 2N > RYD_MAX_QUBITS: RYD_ERR_INVALID, as ryd_observe.
+ *   states_dev  matrix (i, b) starts at states_dev + i*stride_t + b*stride_b (strides in complex128 elements, every
+ *               offset 64-bit), is row-major 2^N x 2^N, contiguous, and is observed at times[i].  Both strides must be
+ *               at least 4^N, else RYD_ERR_INVALID.
+ *   batch       the handle's batch is n_batch (entry b observed with problem b) or 1 (the one problem serves every b),
+ *               as for ryd_observe_many; anything else is RYD_ERR_INVALID.
+ *   times       host float64[n_times], in any order, repeats allowed, resolved as ryd_observe resolves its time.
+ *   what        the RYD_OBS_OCCUPATION / _CORRELATION / _ENERGY bits; a set RYD_OBS_DENSITY bit is ignored.
+ *   out_dev     float64[n_times][n_batch][N*N + N + 3], the layout of ryd_observe.  Zeroed first; slots not asked for
+ *               are exactly 0; the trace (slot N) is always written (by the pair launch, or by the energy kernel when
+ *               no pair launch runs).
+ * Launches: k_obs_pairs on the diagonals, k_eval_coefs_many, and k_obs_energy_dm_many (k_observe.hpp), which adds up
+ * exactly the stored elements and factors that ryd_observe's k_obs_energy_dm adds - rho read as stored, not assumed
+ * Hermitian, the real part kept - but reads them row by row in aligned 128-byte pieces:
+ * 1 + (N-3) + (N-3)(N-4)/2 pieces per row for N >= 3.  Agrees with ryd_observe within the sum of the two calls' rounding
+ * bounds (other summation order), not bit for bit.  ryd_stats.n_applications does not move, n_launches counts the
+ * launches made.  n_times = 0 returns RYD_OK and touches nothing.  The coefficient table of all times, the pinned
+ * upload buffer and its event are those of ryd_observe_many: owned by the handle, grown on demand, freed with it.  No
+ * host synchronisation except while that scratch grows.  One stream per handle, as for ryd_observe_many. */
+int ryd_observe_density_many(ryd_handle* h, const void* states_dev, int32_t n_times, int32_t n_batch,
+                             int64_t stride_t, int64_t stride_b, const double* times, int32_t what,
+                             double* out_dev, void* stream);
+
 /* ryd_observe for a general-path handle - the d-level states of the 3-level "all" basis, leakage (d = 3 / 4) and XY
  * mode, where the reference evaluates the same observables (default_observables.py:291-580 with H(t) of
  * qutip_backend.py:259-264) through dense d^N operators.  `what`, the layout of out_dev (float64[batch][N*N + N + 3],

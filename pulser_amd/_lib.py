@@ -127,6 +127,8 @@ SYMBOLS = {
     "ryd_observe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]),
     "ryd_observe_many": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
                                    C.c_int32, C.c_void_p, C.c_void_p]),
+    "ryd_observe_density_many": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                           C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ryd_general_observe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_void_p, C.c_void_p]),
     "ryd_general_observe_many": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,

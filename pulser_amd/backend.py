@@ -256,7 +256,8 @@ def _one_digit(eigenstates: Sequence[str], one_state: str | None) -> int | None:
 class _DeferredRydState(RydState):
     """The ``RydState`` of a device snapshot that nobody has read yet: ``RydState(lazy.unit(), ...)`` built on the
     first access to its data.  ``eigenstates``, ``n_qudits``, ``qudit_dim`` and ``infer_one_state`` need no data, so
-    an evaluation time whose observables were all served by ``Engine.observe_many`` costs no device-to-host copy;
+    an evaluation time whose observables were all served by ``Engine.observe_many`` (kets) or
+    ``Engine.observe_density_many`` (density matrices: ``unit()`` divides by the trace norm) costs no device-to-host copy;
     whoever does read the state (``StateResult``, ``BitStrings``, ``Fidelity``, ``Expectation``, a callback) gets
     exactly the state the eager construction gives."""
 
@@ -1542,8 +1543,8 @@ def _observe_many_route(states: Sequence[Any], fires: Sequence[bool], engine: An
     ``HamiltonianOperator.observe`` would serve - a ket engine of batch 1 whose ``local_dim`` (2 - 4) is the number of
     eigenstates and whose dimension is ``local_dim ** n`` - and, when the energy moments are wanted (``energy``), one
     without collapse operators that applies its generator through the padded site tables
-    (``GeneralEngine.apply_path()``).  Everything else - the initial state, states already read, spilled stores, density
-    matrices - keeps the per-time path."""
+    (``GeneralEngine.apply_path()``).  Everything else - the initial state, states already read, spilled stores - keeps
+    the per-time path; the density matrices of a two-level master-equation run have ``_observe_density_many_route``."""
     if min_times is None or engine is None or not hasattr(engine, "observe_many"):
         return None
     if hasattr(engine, "local_dim"):
@@ -1581,6 +1582,43 @@ def _observe_many_route(states: Sequence[Any], fires: Sequence[bool], engine: An
     return store, b, positions
 
 
+def _observe_density_many_route(states: Sequence[Any], fires: Sequence[bool], engine: Any, n_eigenstates: int,
+                                min_times: int | None) -> tuple[Any, int, list[int]] | None:
+    """The sibling of ``_observe_many_route`` for two-level master-equation runs: which density matrices of one
+    ``CoherentResults`` a single ``Engine.observe_density_many`` call serves, as (store, sequence of the store,
+    positions into ``states``), or None when the per-time path serves them all.  A position qualifies when a built-in
+    occupation / correlation / energy observable fires there (``fires``) and its state is an unread non-ket
+    ``LazyState`` of one ``SnapshotStore`` whose tensor ``[times, sequences, dim, dim]`` is still on the GPU.  At least
+    ``max(min_times, QutipBackendV2._DENSITY_OBSERVE_MANY_FLOOR)`` positions must qualify (None: the path is off).  The
+    engine is the noiseless 2-level Ising ``Engine`` of one problem in sesolve mode, without quantum jumps and extra
+    detuning terms.  Everything else - the initial state, states already read, spilled stores, ``DeviceState`` results
+    (1 GiB and more per matrix), general engines - keeps the per-time path."""
+    if (min_times is None or engine is None or hasattr(engine, "local_dim")
+            or not hasattr(engine, "observe_density_many") or n_eigenstates != 2):
+        return None
+    if getattr(engine, "batch", 0) != 1 or getattr(engine, "mode", None) != 0 or getattr(engine, "monte_carlo", False):
+        return None  # (mode 0 = RYD_SESOLVE)
+    dterms = getattr(getattr(engine, "tables", None), "dterms", None)
+    if dterms is not None and len(dterms):
+        return None
+    store, b = None, 0
+    positions: list[int] = []
+    for pos, (st, f) in enumerate(zip(states, fires)):
+        if not f or not isinstance(st, LazyState) or st._store is None or st.isket:
+            continue
+        if store is None:
+            dev = st._store.device_tensor
+            if (dev is None or not getattr(dev, "is_cuda", False) or getattr(dev, "dim", lambda: 0)() != 4
+                    or int(dev.shape[2]) != engine.dim or int(dev.shape[3]) != engine.dim):
+                continue
+            store, b = st._store, st._b
+        if st._store is store and st._b == b and tuple(st.shape) == (engine.dim, engine.dim):
+            positions.append(pos)
+    if store is None or len(positions) < max(int(min_times), QutipBackendV2._DENSITY_OBSERVE_MANY_FLOOR):
+        return None
+    return store, b, positions
+
+
 # ------------------------------------------------------------------- backend
 class QutipBackendV2:
     """qutip_backend.py:121-325 on the MI355X engine.  ``sequence`` is a
@@ -1600,6 +1638,11 @@ class QutipBackendV2:
     # The general engines' one-call route never opens below this many times, whatever the threshold above says: the
     # per-time launch counts of short multi-level / XY runs are part of what the suite pins.
     _GENERAL_OBSERVE_MANY_FLOOR = 128
+    # The density matrices of a two-level master-equation run (dephasing, relaxation, depolarizing noise) go through ONE
+    # Engine.observe_density_many call from max(observe_many_min_times, this floor) evaluation times on: the per-time
+    # launch counts of short master-equation runs are part of what the suite pins.  (Measured,
+    # profiles/observe_density_many.md: the one-call path won at every count from 128 on, so the break-even lies below it.)
+    _DENSITY_OBSERVE_MANY_FLOOR = 128
 
     def __init__(self, sequence: Any, *, config: QutipConfig | None = None,
                  mimic_qpu: bool = False) -> None:
@@ -1735,6 +1778,9 @@ class QutipBackendV2:
             eng = noiseless_engine()
             need = max(int(min_times), QutipBackendV2._GENERAL_OBSERVE_MANY_FLOOR) if hasattr(eng, "local_dim") else min_times
             route = _observe_many_route([r.state for r in rs], fires, eng, len(eigenstates), need, wants_energy)
+            density = route is None  # no kets to serve: the density matrices of a two-level master-equation run?
+            if density:
+                route = _observe_density_many_route([r.state for r in rs], fires, eng, len(eigenstates), min_times)
             if route is None:
                 return {}
             store, b, positions = route
@@ -1758,7 +1804,9 @@ class QutipBackendV2:
                     import torch
 
                     x = dev[torch.as_tensor(idx, dtype=torch.long, device=dev.device)]
-                if hasattr(eng, "local_dim"):  # (only the first call carries the energy moments)
+                if density:
+                    got = {0: eng.observe_density_many(x, times_us, energy=wants_energy)}
+                elif hasattr(eng, "local_dim"):  # (only the first call carries the energy moments)
                     got = {d: eng.observe_many(x, times_us, one=d, energy=wants_energy and k == 0)
                            for k, d in enumerate(digits)}
                 else:

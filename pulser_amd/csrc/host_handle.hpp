@@ -184,7 +184,7 @@ struct ryd_handle {
   cplx* gen_obs_scratch = nullptr;
   size_t gen_obs_scratch_bytes = 0;
   bool gen_obs_small_chunks = false;  // test hook: 5 columns per chunk
-  // ryd_observe_many: [n_times] ObsManyTime, then the coefficient table [n_times][B][N][4] (grown on demand), and the
+  // ryd_observe_many / ryd_observe_density_many: [n_times] ObsManyTime, then the coefficient table [n_times][B][N][4] (grown on demand), and the
   // pinned host copy of the former with the event that says its last upload has been read.  ryd_general_observe_many (a
   // general handle never takes the two-level call): the same record list, then tcoef[n_terms] and mvals[E + Dg] per time
   void* obs_many_dev = nullptr;

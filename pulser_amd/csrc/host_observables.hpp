@@ -164,6 +164,56 @@ extern "C" int ryd_general_observe(ryd_handle* h, const void* state_dev, double 
   return RYD_OK;
 }
 
+// The scratch of the *_many calls, owned by the handle: [n_times] ObsManyTime - the (interval, offset) of every time, found
+// on the host exactly as ryd_observe finds it and uploaded from a pinned copy - followed by `table_bytes` for the caller's
+// coefficient table.  Grows on demand (the only host synchronisation); calls on one handle are ordered by using ONE
+// stream, as with coefs_dev / wA of ryd_observe.
+static int obs_many_stage_times(ryd_handle* h, int n_times, const double* times, size_t table_bytes, hipStream_t st,
+                                ObsManyTime** tm_dev, void** table) {
+  const size_t tm_bytes = ((size_t)n_times * sizeof(ObsManyTime) + 255) & ~(size_t)255;
+  const size_t need = tm_bytes + table_bytes;
+  if (need > h->obs_many_bytes) {
+    HIPCHK(hipStreamSynchronize(st));  // (an earlier call on this stream may still read the old scratch)
+    if (h->obs_many_dev) HIPCHK(hipFree(h->obs_many_dev));
+    h->obs_many_dev = nullptr;
+    h->obs_many_bytes = 0;
+    HIPCHK(hipMalloc(&h->obs_many_dev, need));
+    h->obs_many_bytes = need;
+  }
+  if (!h->obs_many_ev) HIPCHK(hipEventCreateWithFlags(&h->obs_many_ev, hipEventDisableTiming));
+  else HIPCHK(hipEventSynchronize(h->obs_many_ev));  // the last upload has left the pinned buffer
+  if ((size_t)n_times > h->obs_many_pin_cap) {
+    if (h->obs_many_pin) HIPCHK(hipHostFree(h->obs_many_pin));
+    h->obs_many_pin = nullptr;
+    h->obs_many_pin_cap = 0;
+    HIPCHK(hipHostMalloc((void**)&h->obs_many_pin, (size_t)n_times * sizeof(ObsManyTime), hipHostMallocDefault));
+    h->obs_many_pin_cap = (size_t)n_times;
+  }
+  for (int i = 0; i < n_times; ++i) {
+    const MixPoint m = mix_at(h, times[i]);
+    h->obs_many_pin[i] = {m.u1, m.idx1, 0};
+  }
+  *tm_dev = (ObsManyTime*)h->obs_many_dev;
+  *table = (char*)h->obs_many_dev + tm_bytes;
+  HIPCHK(hipMemcpyAsync(*tm_dev, h->obs_many_pin, (size_t)n_times * sizeof(ObsManyTime), hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(h->obs_many_ev, st));
+  return RYD_OK;
+}
+
+// the coefficient table [n_times][B][N][4] of k_eval_coefs_many in the handle's scratch: one upload, one launch
+static int obs_many_coef_table(ryd_handle* h, int n_times, const double* times, hipStream_t st, double** table) {
+  const int B = h->B, N = h->N;
+  ObsManyTime* tm_dev = nullptr;
+  int rc = obs_many_stage_times(h, n_times, times, (size_t)n_times * B * N * 4 * sizeof(double), st, &tm_dev, (void**)table);
+  if (rc) return rc;
+  const long long total = (long long)n_times * B * N;
+  hipLaunchKernelGGL(k_eval_coefs_many, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const cplx*)h->pp_dev,
+                     h->n_knots - 1, (const ryd_qdesc*)h->desc_dev, (const ObsManyTime*)tm_dev, B * N, total, *table);
+  HIPCHK(hipGetLastError());
+  h->stats.n_launches++;
+  return RYD_OK;
+}
+
 // ryd_observe for every evaluation time of a run (two-level Ising kets): the second half of k_observe.hpp
 extern "C" int ryd_observe_many(ryd_handle* h, const void* states_dev, int32_t n_times, int32_t n_batch,
                                 int64_t stride_t, int64_t stride_b, const double* times, int32_t what,
@@ -202,41 +252,61 @@ extern "C" int ryd_observe_many(ryd_handle* h, const void* states_dev, int32_t n
   }
   if (!(what & RYD_OBS_ENERGY)) return RYD_OK;
   // the (interval, offset) of every time on the host, the table of every time in one launch
-  // (the scratch is the handle's: calls on one handle are ordered by using ONE stream, as with coefs_dev / wA of ryd_observe)
-  const size_t tm_bytes = ((size_t)n_times * sizeof(ObsManyTime) + 255) & ~(size_t)255;
-  const size_t need = tm_bytes + (size_t)n_times * B * N * 4 * sizeof(double);
-  if (need > h->obs_many_bytes) {
-    HIPCHK(hipStreamSynchronize(st));  // (an earlier call on this stream may still read the old scratch)
-    if (h->obs_many_dev) HIPCHK(hipFree(h->obs_many_dev));
-    h->obs_many_dev = nullptr;
-    h->obs_many_bytes = 0;
-    HIPCHK(hipMalloc(&h->obs_many_dev, need));
-    h->obs_many_bytes = need;
-  }
-  if (!h->obs_many_ev) HIPCHK(hipEventCreateWithFlags(&h->obs_many_ev, hipEventDisableTiming));
-  else HIPCHK(hipEventSynchronize(h->obs_many_ev));  // the last upload has left the pinned buffer
-  if ((size_t)n_times > h->obs_many_pin_cap) {
-    if (h->obs_many_pin) HIPCHK(hipHostFree(h->obs_many_pin));
-    h->obs_many_pin = nullptr;
-    h->obs_many_pin_cap = 0;
-    HIPCHK(hipHostMalloc((void**)&h->obs_many_pin, (size_t)n_times * sizeof(ObsManyTime), hipHostMallocDefault));
-    h->obs_many_pin_cap = (size_t)n_times;
-  }
-  for (int i = 0; i < n_times; ++i) {
-    const MixPoint m = mix_at(h, times[i]);
-    h->obs_many_pin[i] = {m.u1, m.idx1, 0};
-  }
-  ObsManyTime* tm_dev = (ObsManyTime*)h->obs_many_dev;
-  double* table = (double*)((char*)h->obs_many_dev + tm_bytes);
-  HIPCHK(hipMemcpyAsync(tm_dev, h->obs_many_pin, (size_t)n_times * sizeof(ObsManyTime), hipMemcpyHostToDevice, st));
-  HIPCHK(hipEventRecord(h->obs_many_ev, st));
-  const long long total = (long long)n_times * B * N;
-  hipLaunchKernelGGL(k_eval_coefs_many, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const cplx*)h->pp_dev,
-                     h->n_knots - 1, (const ryd_qdesc*)h->desc_dev, (const ObsManyTime*)tm_dev, B * N, total, table);
-  HIPCHK(hipGetLastError());
-  h->stats.n_launches++;
+  double* table = nullptr;
+  if ((rc = obs_many_coef_table(h, n_times, times, st, &table))) return rc;
   const unsigned gx = (unsigned)std::max<int64_t>(D >> kObsManyTB, 1);
   hipLaunchKernelGGL(k_obs_energy_many, dim3(gx, gy), dim3(256), 0, st, (const cplx*)states_dev, n_states, (int)n_batch,
+                     (long long)stride_t, (long long)stride_b, N, (const double*)table, B, (const double*)h->e0_dev,
+                     h->e0_mats == 1 ? 0ll : (long long)D, pairs ? 0 : 1, out_dev, stride);
+  HIPCHK(hipGetLastError());
+  h->stats.n_launches++;
+  return RYD_OK;
+}
+
+// ryd_observe + RYD_OBS_DENSITY for every density matrix of a master-equation run: k_obs_pairs on the diagonals,
+// k_eval_coefs_many, k_obs_energy_dm_many (the end of k_observe.hpp)
+extern "C" int ryd_observe_density_many(ryd_handle* h, const void* states_dev, int32_t n_times, int32_t n_batch,
+                                        int64_t stride_t, int64_t stride_b, const double* times, int32_t what,
+                                        double* out_dev, void* stream) {
+  if (!h) return fail(RYD_ERR_INVALID, "null handle");
+  if (h->general) return fail(RYD_ERR_INVALID, "observe_density_many: not available on a general-path handle");
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (h->mc)
+    return fail(RYD_ERR_UNSUPPORTED, "observe_density_many: Monte-Carlo handles are not served (use ryd_observe)");
+  if (!h->dterms_host.empty())
+    return fail(RYD_ERR_UNSUPPORTED, "observe_density_many: handles with extra detuning terms are not served (use ryd_observe)");
+  const int N = h->N, B = h->B;
+  if (2 * N > RYD_MAX_QUBITS) return fail(RYD_ERR_INVALID, "2N exceeds %d", RYD_MAX_QUBITS);
+  const int64_t D = (int64_t)1 << N;
+  if (n_times < 0 || n_batch < 1) return fail(RYD_ERR_INVALID, "observe_density_many: %d times, batch %d", n_times, n_batch);
+  if (B != n_batch && B != 1)
+    return fail(RYD_ERR_INVALID, "observe_density_many: a handle of batch %d cannot observe %d states per time (its batch or 1)", B, n_batch);
+  if (stride_t < D * D || stride_b < D * D)
+    return fail(RYD_ERR_INVALID, "observe_density_many: strides %lld / %lld are smaller than a density matrix of %lld elements",
+                (long long)stride_t, (long long)stride_b, (long long)(D * D));
+  if (n_times == 0) return RYD_OK;
+  if (!states_dev || !times || !out_dev) return fail(RYD_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->cfg.device));
+  hipStream_t st = (hipStream_t)stream;
+  const int stride = N * N + N + 3;
+  const long long n_states = (long long)n_times * n_batch;
+  HIPCHK(hipMemsetAsync(out_dev, 0, (size_t)n_states * stride * sizeof(double), st));
+  const unsigned gy = (unsigned)std::min<long long>(n_states, 65535);
+  // (the trace comes with the pair kernel, or with the energy kernel of an energy-only call)
+  const bool pairs = (what & (RYD_OBS_OCCUPATION | RYD_OBS_CORRELATION)) || !(what & RYD_OBS_ENERGY);
+  if (pairs) {
+    hipLaunchKernelGGL(k_obs_pairs, dim3((unsigned)((D + 2047) / 2048), gy), dim3(256), 0, st, (const cplx*)states_dev,
+                       n_states, (int)n_batch, (long long)stride_t, (long long)stride_b, N, 1, (int)what, out_dev, stride);
+    HIPCHK(hipGetLastError());
+    h->stats.n_launches++;
+  }
+  if (!(what & RYD_OBS_ENERGY)) return RYD_OK;
+  double* table = nullptr;
+  if ((rc = obs_many_coef_table(h, n_times, times, st, &table))) return rc;
+  // a workgroup takes 32 rows at a time; 256 rows per workgroup where the matrix has that many
+  const unsigned gx = (unsigned)std::min<int64_t>(std::max<int64_t>(D >> 8, 1), 1024);
+  hipLaunchKernelGGL(k_obs_energy_dm_many, dim3(gx, gy), dim3(256), 0, st, (const cplx*)states_dev, n_states, (int)n_batch,
                      (long long)stride_t, (long long)stride_b, N, (const double*)table, B, (const double*)h->e0_dev,
                      h->e0_mats == 1 ? 0ll : (long long)D, pairs ? 0 : 1, out_dev, stride);
   HIPCHK(hipGetLastError());
@@ -304,33 +374,9 @@ extern "C" int ryd_general_observe_many(ryd_handle* h, const void* states_dev, i
   size_t chunk = std::max<size_t>(kGenObsScratchCap / (per_time * sizeof(cplx)), 1);
   if (h->gen_obs_small_chunks) chunk = std::min<size_t>(chunk, 5);
   chunk = std::min<size_t>(chunk, (size_t)n_times);
-  const size_t tm_bytes = ((size_t)n_times * sizeof(ObsManyTime) + 255) & ~(size_t)255;
-  const size_t need = tm_bytes + chunk * per_time * sizeof(cplx);
-  if (need > h->obs_many_bytes) {
-    HIPCHK(hipStreamSynchronize(st));  // (an earlier call on this stream may still read the old scratch)
-    if (h->obs_many_dev) HIPCHK(hipFree(h->obs_many_dev));
-    h->obs_many_dev = nullptr;
-    h->obs_many_bytes = 0;
-    HIPCHK(hipMalloc(&h->obs_many_dev, need));
-    h->obs_many_bytes = need;
-  }
-  if (!h->obs_many_ev) HIPCHK(hipEventCreateWithFlags(&h->obs_many_ev, hipEventDisableTiming));
-  else HIPCHK(hipEventSynchronize(h->obs_many_ev));  // the last upload has left the pinned buffer
-  if ((size_t)n_times > h->obs_many_pin_cap) {
-    if (h->obs_many_pin) HIPCHK(hipHostFree(h->obs_many_pin));
-    h->obs_many_pin = nullptr;
-    h->obs_many_pin_cap = 0;
-    HIPCHK(hipHostMalloc((void**)&h->obs_many_pin, (size_t)n_times * sizeof(ObsManyTime), hipHostMallocDefault));
-    h->obs_many_pin_cap = (size_t)n_times;
-  }
-  for (int i = 0; i < n_times; ++i) {
-    const MixPoint m = mix_at(h, times[i]);
-    h->obs_many_pin[i] = {m.u1, m.idx1, 0};
-  }
-  ObsManyTime* tm_dev = (ObsManyTime*)h->obs_many_dev;
-  cplx* table = (cplx*)((char*)h->obs_many_dev + tm_bytes);
-  HIPCHK(hipMemcpyAsync(tm_dev, h->obs_many_pin, (size_t)n_times * sizeof(ObsManyTime), hipMemcpyHostToDevice, st));
-  HIPCHK(hipEventRecord(h->obs_many_ev, st));
+  ObsManyTime* tm_dev = nullptr;
+  cplx* table = nullptr;
+  if ((rc = obs_many_stage_times(h, n_times, times, chunk * per_time * sizeof(cplx), st, &tm_dev, (void**)&table))) return rc;
   {
     static bool attr[64] = {};
     const int dev = h->cfg.device;

@@ -97,6 +97,49 @@ __global__ __launch_bounds__(256) void k_obs_energy(const cplx* __restrict__ x, 
 //                               (H^2)_{a,a^k^l} = 2 h_k(a) h_l(a)      (k != l)
 // so one thread per row index a gathers 1 + N + N(N-1)/2 elements of column a.  No H(t) is built
 // (qutip_backend.py:259-264 materialises it) and rho is not multiplied by anything dense.
+
+// E(s) = e0[s] - sum_{k: bit_k(s) = 0} delta_k (atom k on bit N-1-k; cf = the (Re c, Im c, delta, 0) rows of one time)
+__device__ __forceinline__ double obs_dm_diag(const double* e0b, const double* cf, int N, size_t s) {
+  double e = e0b[s];
+  for (int k = 0; k < N; ++k)
+    if (!((s >> (N - 1 - k)) & 1)) e -= cf[4 * k + 2];
+  return e;
+}
+
+// sum_k |c_k|^2
+__device__ __forceinline__ double obs_dm_c2(const double* cf, int N) {
+  double c2 = 0.0;
+  for (int k = 0; k < N; ++k) c2 += cf[4 * k] * cf[4 * k] + cf[4 * k + 1] * cf[4 * k + 1];
+  return c2;
+}
+
+// What ONE stored element x = rho[r][c] adds to e1 = Tr(H rho) and e2 = Tr(H^2 rho) - the arithmetic of both density
+// kernels, k_obs_energy_dm (a thread gathers column c) and k_obs_energy_dm_many (eight lanes read a 128-byte piece of
+// row r).  `flips` = popcount(r ^ c): 0 - the diagonal; 1 - r ^ c is the bit of atom k; 2 - the bits of atoms k < l;
+// anything else adds nothing.  rho is read as stored (not assumed Hermitian) and the real part is kept.
+// Er = E(r), Ec = E(c), c2 = sum_k |c_k|^2; k, l are read only where `flips` says so.
+__device__ __forceinline__ void obs_dm_add(const cplx x, const int flips, const int k, const int l, const size_t c,
+                                           const int N, const double* cf, const double Er, const double Ec,
+                                           const double c2, double& e1, double& e2) {
+  if (flips == 0) {
+    e1 += Ec * x.x;
+    e2 += (Ec * Ec + c2) * x.x;
+  } else if (flips == 1 || flips == 2) {
+    const bool bk = (c >> (N - 1 - k)) & 1;
+    const cplx hk = make_double2(cf[4 * k], bk ? cf[4 * k + 1] : -cf[4 * k + 1]);  // h_k(c)
+    if (flips == 1) {
+      const double re = hk.x * x.x - hk.y * x.y;  // Re(h_k rho_{c^k,c}); the imaginary parts cancel in the trace
+      e1 += re;
+      e2 += re * (Ec + Er);
+    } else {
+      const bool bl = (c >> (N - 1 - l)) & 1;
+      const cplx hl = make_double2(cf[4 * l], bl ? cf[4 * l + 1] : -cf[4 * l + 1]);
+      const cplx hh = cmul(hk, hl);
+      e2 += 2.0 * (hh.x * x.x - hh.y * x.y);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void k_obs_energy_dm(const cplx* __restrict__ rho, int N,
                                                        const double* __restrict__ coefs,
                                                        const double* __restrict__ e0, long long e0_stride,
@@ -108,33 +151,14 @@ __global__ __launch_bounds__(256) void k_obs_energy_dm(const cplx* __restrict__ 
   const double* e0b = e0 + (size_t)b * e0_stride;
   double e1 = 0.0, e2 = 0.0;
   for (size_t a = (size_t)blockIdx.x * 256 + threadIdx.x; a < D; a += (size_t)gridDim.x * 256) {
-    auto energy = [&](size_t s) {
-      double e = e0b[s];
-      for (int k = 0; k < N; ++k)
-        if (!((s >> (N - 1 - k)) & 1)) e -= cf[4 * k + 2];
-      return e;
-    };
-    const double Ea = energy(a);
-    double c2 = 0.0;
-    for (int k = 0; k < N; ++k) c2 += cf[4 * k] * cf[4 * k] + cf[4 * k + 1] * cf[4 * k + 1];
-    const double raa = r[a * D + a].x;
-    e1 += Ea * raa;
-    e2 += (Ea * Ea + c2) * raa;
+    const double Ea = obs_dm_diag(e0b, cf, N, a);
+    const double c2 = obs_dm_c2(cf, N);
+    obs_dm_add(r[a * D + a], 0, 0, 0, a, N, cf, Ea, Ea, c2, e1, e2);
     for (int k = 0; k < N; ++k) {
       const size_t ak = a ^ ((size_t)1 << (N - 1 - k));
-      const bool bk = (a >> (N - 1 - k)) & 1;
-      const cplx hk = make_double2(cf[4 * k], bk ? cf[4 * k + 1] : -cf[4 * k + 1]);
-      const cplx x = r[ak * D + a];  // rho_{a^k, a}
-      const double re = hk.x * x.x - hk.y * x.y;  // Re(h_k rho_{a^k,a}); the imaginary parts cancel in the trace
-      e1 += re;
-      e2 += re * (Ea + energy(ak));
-      for (int l = k + 1; l < N; ++l) {
-        const bool bl = (a >> (N - 1 - l)) & 1;
-        const cplx hl = make_double2(cf[4 * l], bl ? cf[4 * l + 1] : -cf[4 * l + 1]);
-        const cplx hh = cmul(hk, hl);
-        const cplx y = r[(ak ^ ((size_t)1 << (N - 1 - l))) * D + a];
-        e2 += 2.0 * (hh.x * y.x - hh.y * y.y);
-      }
+      obs_dm_add(r[ak * D + a], 1, k, 0, a, N, cf, obs_dm_diag(e0b, cf, N, ak), Ea, c2, e1, e2);  // rho_{a^k, a}
+      for (int l = k + 1; l < N; ++l)
+        obs_dm_add(r[(ak ^ ((size_t)1 << (N - 1 - l))) * D + a], 2, k, l, a, N, cf, 0.0, Ea, c2, e1, e2);
     }
   }
 #pragma unroll
@@ -260,5 +284,90 @@ __global__ __launch_bounds__(256) void k_obs_energy_many(const cplx* __restrict_
       atomicAdd(out + (size_t)s * out_stride + (j < 2 ? off + j : N), v);
     }
     __syncthreads();  // `tile`, `cf` and `part` are written again for the next state of this workgroup
+  }
+}
+
+// ---------------------------------------------------------------------------
+// ryd_observe_density_many: Tr(H rho), Tr(H^2 rho) of EVERY density matrix of a master-equation run in one launch
+// ---------------------------------------------------------------------------
+// k_obs_energy_dm gives lane a the elements rho[(a ^ m) * D + a] of COLUMN a: the 64 lanes of a wave read 64 different
+// rows, one 16-byte element each.  Here the work is organised by the ROW that holds the elements (rho is row-major):
+// of row r the sums need the columns c = r ^ m with popcount(m) <= 2, and with m = hi | lo (lo = the low three bits)
+// the eight columns (r ^ hi) ^ lo, lo = 0 .. 7, are ONE aligned 128-byte piece of the row.  Eight lanes read it with
+// one 16-byte load each, so a wave instruction covers eight whole 128-byte pieces (of eight consecutive rows), and the
+// pieces fetched per row are, for N >= 3,
+//   hi = 0:                   1 piece,                 7 of its 8 elements add something (lo = 7 flips three atoms)
+//   hi = one higher bit:      N - 3 pieces,            4 of 8 (lo = 0: that atom alone; one low bit: a pair)
+//   hi = two higher bits:     (N - 3)(N - 4) / 2,      1 of 8 (lo = 0)
+// = 1 + (N - 3) + (N - 3)(N - 4) / 2 pieces of 128 bytes (29 of the 128 of a 10-atom row).  An element that adds
+// nothing costs its lane nothing but the load: obs_dm_add ignores more than two flips.  Registers of N < 3 atoms have
+// rows of 2 or 4 elements, read by the first 2 or 4 lanes of a group.
+// The piece is the same for the eight groups of a wave (and the four waves of the workgroup), so whether E(c) is needed
+// (one flip: only where hi has at most one bit) is uniform: the loops over the pieces do not diverge.  E(r) is formed
+// once per row and lane, E(c) by the lanes that need it (e0 is 2^N doubles per problem and stays in cache); the 4N
+// coefficients of the state's time are staged in LDS once per state.  Partial sums: __shfl_down, LDS across the four
+// waves, one fp64 atomicAdd pair per workgroup and state (k_obs_energy_many's pattern).  State s = it * n_batch + b
+// comes from the second grid axis with a stride (capped at 65 535), its coefficients are row (it, hb) of the table of
+// k_eval_coefs_many, hb = b or 0 (handle_batch = 1).  Rows: group g of workgroup x takes r = 32 x + g, + 32 gridDim.x, ...
+// `with_norm`: also out[s][N] += sum_r Re rho_rr (energy-only calls, where k_obs_pairs does not run).
+__global__ __launch_bounds__(256) void k_obs_energy_dm_many(const cplx* __restrict__ states, long long n_states,
+                                                            int n_batch, long long stride_t, long long stride_b, int N,
+                                                            const double* __restrict__ coefs, int handle_batch,
+                                                            const double* __restrict__ e0, long long e0_stride,
+                                                            int with_norm, double* __restrict__ out, int out_stride) {
+  __shared__ double cf[4 * RYD_MAX_QUBITS];
+  __shared__ double part[4][3];
+  const unsigned D = 1u << N;
+  const unsigned g = threadIdx.x >> 3, lo = threadIdx.x & 7;
+  const int off = N * N + N + 1;
+  for (long long s = blockIdx.y; s < n_states; s += gridDim.y) {
+    const long long it = s / n_batch, b = s - it * n_batch;
+    const long long hb = handle_batch == 1 ? 0 : b;
+    const cplx* st = states + it * stride_t + b * stride_b;
+    const double* cfg = coefs + ((size_t)it * handle_batch + hb) * N * 4;
+    const double* e0b = e0 + hb * e0_stride;
+    for (int i = threadIdx.x; i < 4 * N; i += 256) cf[i] = cfg[i];
+    __syncthreads();
+    const double c2 = obs_dm_c2(cf, N);
+    double e1 = 0.0, e2 = 0.0, nrm = 0.0;
+    for (unsigned r = blockIdx.x * 32 + g; r < D; r += gridDim.x * 32) {
+      const cplx* row = st + (size_t)r * D;
+      const double Er = obs_dm_diag(e0b, cf, N, r);
+      // the piece of row r that holds column r ^ hi; `one`: some lane of it is one flip away from r
+      auto piece = [&](const unsigned hi, const bool one) {
+        const unsigned c = ((r ^ hi) & ~7u) | lo;
+        if (c >= D) return;  // (N < 3: a row is shorter than a piece)
+        const unsigned m = r ^ c;
+        const int flips = __popc(m);
+        // atoms k < l of the flipped bits (atom k on bit N-1-k): k from the highest set bit, l from the lowest
+        const int k = m ? N - 1 - (31 - __clz((int)m)) : 0, l = m ? N - 1 - (__ffs((int)m) - 1) : 0;
+        const double Ec = flips == 0 ? Er : (one && flips == 1) ? obs_dm_diag(e0b, cf, N, c) : 0.0;
+        const cplx x = row[c];
+        obs_dm_add(x, flips, k, l, c, N, cf, Er, Ec, c2, e1, e2);
+        if (flips == 0) nrm += x.x;
+      };
+      piece(0u, true);
+      for (int p = 3; p < N; ++p) piece(1u << p, true);
+      for (int p = 3; p < N; ++p)
+        for (int q = p + 1; q < N; ++q) piece((1u << p) | (1u << q), false);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      e1 += __shfl_down(e1, o, 64);
+      e2 += __shfl_down(e2, o, 64);
+      nrm += __shfl_down(nrm, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      part[threadIdx.x >> 6][0] = e1;
+      part[threadIdx.x >> 6][1] = e2;
+      part[threadIdx.x >> 6][2] = nrm;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && (threadIdx.x < 2 || with_norm)) {
+      const int j = threadIdx.x;
+      const double v = (part[0][j] + part[1][j]) + (part[2][j] + part[3][j]);
+      atomicAdd(out + (size_t)s * out_stride + (j < 2 ? off + j : N), v);
+    }
+    __syncthreads();  // `cf` and `part` are written again for the next state of this workgroup
   }
 }

@@ -584,6 +584,42 @@ class Engine:
                                              what, out.data_ptr(), self._stream()))
         return _obs_unpack(out, n)
 
+    def observe_density_many(self, states: Any, times: Any, occupation: bool = True, correlation: bool = True,
+                             energy: bool = True) -> dict[str, np.ndarray]:
+        """``ryd_observe_density_many``: what ``observe(..., density=True)`` returns, for the density matrices of every
+        evaluation time of a master-equation run in one device call (a memset and at most three launches) and one
+        device-to-host copy.  ``states`` is a complex128 tensor ``[T, B, D, D]`` (``D = 2 ** n``) on this engine's
+        device, or any view of one whose last two axes are contiguous: the strides of the first two axes are passed
+        on, so ``dev[:, b:b + 1]`` and ``dev[i0:i1:step]`` of a snapshot tensor are observed in place.  ``times`` [T]
+        (us) need not be sorted or distinct.  ``B`` is this engine's batch (entry b has problem b) or anything when the
+        batch is 1.  Two-level Ising engines in sesolve mode (the Hamiltonian is this engine's, as with ``density=True``)
+        or mesolve mode, without quantum jumps and extra detuning terms.  Returns host arrays ``norm2`` [T, B] (the
+        trace), ``occupation`` [T, B, N], ``correlation`` [T, B, N, N], ``energy`` [T, B], ``energy2`` [T, B] - NOT
+        normalised (divide by ``norm2``); what was not asked for is 0."""
+        torch = self.torch
+        d = 1 << self.n
+        if not (isinstance(states, torch.Tensor) and states.is_cuda and states.device == self.device):
+            raise ValueError(f"states must be a torch tensor on {self.device}")
+        if states.dtype != torch.complex128:
+            raise ValueError(f"states must be complex128, got {states.dtype}")
+        if states.dim() != 4 or tuple(states.shape[2:]) != (d, d) or int(states.shape[1]) < 1:
+            raise ValueError(f"states must have the shape [T, B >= 1, {d}, {d}], got {tuple(states.shape)}")
+        if states.stride(3) != 1 or states.stride(2) != d:
+            raise ValueError("the last two axes of states must be contiguous (the first two may be strided)")
+        n_t, n_b = int(states.shape[0]), int(states.shape[1])
+        tt = np.ascontiguousarray(times, dtype=np.float64)
+        if tt.shape != (n_t,):
+            raise ValueError(f"need one time per state of the first axis ({n_t}), got {tt.shape}")
+        # (the stride of an axis of length 1 is arbitrary in torch and never used: any valid value will do)
+        stride_b = int(states.stride(1)) if n_b > 1 else d * d
+        stride_t = int(states.stride(0)) if n_t > 1 else max(n_b * stride_b, d * d)
+        n = self.n
+        what = _obs_what(occupation, correlation, energy)
+        out = torch.empty((n_t, n_b, n * n + n + 3), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.ryd_observe_density_many(self._h, states.data_ptr(), n_t, n_b, stride_t, stride_b,
+                                                     tt.ctypes.data, what, out.data_ptr(), self._stream()))
+        return _obs_unpack(out, n)
+
     def occupations(self, state: Any) -> Any:
         """float64[B, N+1]: <n_k> and, last, the squared norm / trace."""
         self._check_state(state)
