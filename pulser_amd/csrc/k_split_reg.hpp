@@ -8,8 +8,9 @@
 // wave bits (64 << NW lanes).  A stage = D (phase) + the N single-atom rotations; every rotation is done where its bit
 // is cheapest to reach:
 //   * register bits: plain FMAs (tan form: x' = x - T y_p, y' = y + T x_p, the same formula on both partners);
-//   * the low ND = 6 - (NR - NW) lane bits: the partner comes over the DPP crossbar (quad permutes, row rotate by 8;
-//     bit 2 takes two hops) - no layout change, no LDS;
+//   * the low ND = 6 - (NR - NW) lane bits: the partner comes over the DPP crossbar (quad permutes, row rotate by 8,
+//     row (half) mirror: every bit's direction is ONE pattern, SPLITR_HM) - no layout change, no LDS; for a real drive
+//     only the imaginary parts travel, as a chain of hops from direction to direction (SPLITR_YCHAIN, split_ychain.hpp);
 //   * the upper NTB = NR - NW lane bits: an INTRA-WAVE transposition through LDS exchanges them with the register bits
 //     NW .. NR-1 ("T bits").  A wave only reads what it wrote itself: no barrier, only the LDS queue's own order, so
 //     the waves of a workgroup drift apart and the transposition of one overlaps the FMAs of another (and, inside a
@@ -82,6 +83,23 @@
 #ifndef SPLITR_LATE_REAL
 #define SPLITR_LATE_REAL 0  /* the same for real drives (A/B) */
 #endif
+//   SPLITR_YCHAIN (real drives, SPLITR_TMODE 1, SPLITR_HM 1, no SPLITR_B2; profiles/ychain.md):
+//                0: every DPP lane bit fetches both parts of its partner (4 moves per amplitude and bit); the stores of the
+//                   pass are issued in one block;
+//                1 (default): the rotation of a DPP bit is two real rotations on the pairs (x(L), y(L ^ m)) and (x(L ^ m), y(L)),
+//                   so the lane keeps its x, holds the partner's y and does both FMAs itself - the same FMAs on the same
+//                   operands, bit for bit the same results; only y travels, from direction to direction (hop plan:
+//                   split_ychain.hpp), and comes home after the last rotation: 12 moves per amplitude instead of 16 with four
+//                   DPP bits.  The chain runs hop by hop over a chunk, and the stores of the previous chunk are spread over
+//                   its steps (write_pre below) - that, not the moves, is most of what was measured;
+//                2: the way home rides on the LDS pass instead (NW > 0, not SPLITR_P5): pass_write stores x to the lane's own
+//                   slot and y to the slot of the lane it belongs to (same wave, same 8-lane group, before the same barrier):
+//                   10 moves per amplitude, but two 8-byte stores per amplitude, 2-way bank conflicts each (measured: not
+//                   faster than 1 beyond the noise)
+#ifndef SPLITR_YCHAIN
+#define SPLITR_YCHAIN 1
+#endif
+#include "split_ychain.hpp"
 
 template <int N, int NR>
 struct SplitRegLayout {
@@ -488,6 +506,9 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
       a = __hiloint2double((int)ahi, (int)alo);
       c = __hiloint2double((int)chi, (int)clo);
     };
+    // SPLITR_YCHAIN: the shapes and builds that take the y chain, and whether its last hop rides on the pass
+    constexpr bool kYChain = SPLITR_YCHAIN != 0 && !CPLX && SPLITR_HM == 1 && SPLITR_TMODE == 1 && !SPLITR_B2 && !(SPLITR_KO & 2) && ND >= 2;
+    constexpr bool kYStore = kYChain && SPLITR_YCHAIN == 2 && NW > 0 && !kP5 && !(SPLITR_KO & 4);
     auto t_swap = [&](auto Gc) {  // SPLITR_TMODE 1 (NTB == 2): T bit 0 <-> lane bit 4, T bit 1 <-> lane bit 5
       constexpr int g = decltype(Gc)::value;
       if (SPLITR_KO & 1) return;
@@ -654,13 +675,41 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
 
     // ---- per chunk (top two T bits fixed): the pass bits and the DPP lane bits, then the pass ----
     constexpr int CM = 3 << (NR - 2);  // the chunk's bits of the register index
-    auto pre = [&](auto Cc) {
+    auto pre_regs = [&](auto Cc) {  // the pass bits
       constexpr int c = decltype(Cc)::value;
       splitr_for<0, NW>([&](auto Jc) { rot_reg(Jc, Tr[decltype(Jc)::value], Ur[decltype(Jc)::value], splitr_c<CM>{}, splitr_c<(c << (NR - 2))>{}); });
-      splitr_for<0, CH>([&](auto Kc) {
-        rot_lane(splitr_c<(decltype(Kc)::value | (c << (NR - 2)))>{}, splitr_c<PMASK>{});
-        if constexpr (SPLITR_TMODE == 3) rot_lane_x(splitr_c<(decltype(Kc)::value | (c << (NR - 2)))>{});
-      });
+    };
+    // SPLITR_YCHAIN: step I of the y chain on the registers of a chunk - the hop to the direction of the plan's I-th bit (one
+    // or two patterns, generated from the table and from nothing else), then that bit's rotation; step ND = the way home
+    // (no pattern when the pass stores y shifted).  Lane L keeps x(L) and holds y(L ^ shift).  Hop by hop over the whole
+    // chunk: CH independent registers between a move and the FMA that waits for it.
+    auto chain_step = [&](auto Cc, auto Ic) {
+      constexpr int c = decltype(Cc)::value, i = decltype(Ic)::value;
+      typedef SplitYPlan<ND, (kYStore ? 1 : 0)> PL;
+      constexpr SplitYHop h = PL::hops[i];
+      if constexpr (h.n > 0) splitr_for<0, CH>([&](auto Kc) { constexpr int r = decltype(Kc)::value | (c << (NR - 2)); xi[r] = splitr_dpp<h.ctrl[0]>(xi[r]); });
+      if constexpr (h.n > 1) splitr_for<0, CH>([&](auto Kc) { constexpr int r = decltype(Kc)::value | (c << (NR - 2)); xi[r] = splitr_dpp<h.ctrl[1]>(xi[r]); });
+      if constexpr (i < ND) {
+        const double T = Tl[PL::order[i < ND ? i : 0]];
+        splitr_for<0, CH>([&](auto Kc) {
+          constexpr int r = decltype(Kc)::value | (c << (NR - 2));
+          const double x0 = xr[r];
+          xr[r] = fma(-T, xi[r], x0);  // x'(L) = x(L) - T y(L ^ m)
+          xi[r] = fma(T, x0, xi[r]);   // y'(L ^ m) = y(L ^ m) + T x(L)
+        });
+      }
+    };
+    auto pre = [&](auto Cc) {
+      constexpr int c = decltype(Cc)::value;
+      pre_regs(Cc);
+      if constexpr (kYChain) {
+        splitr_for<0, ND + 1>([&](auto Ic) { chain_step(Cc, Ic); });
+      } else {
+        splitr_for<0, CH>([&](auto Kc) {
+          rot_lane(splitr_c<(decltype(Kc)::value | (c << (NR - 2)))>{}, splitr_c<PMASK>{});
+          if constexpr (SPLITR_TMODE == 3) rot_lane_x(splitr_c<(decltype(Kc)::value | (c << (NR - 2)))>{});
+        });
+      }
     };
     auto post = [&](auto Cc) {  // the wave bits, now register bits 0 .. NW-1
       constexpr int c = decltype(Cc)::value;
@@ -668,13 +717,44 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
     };
     // slot = l + 64 (A + NG (B + NG s)):  writer A = wave, B = its pass bits;  reader A = its pass bits, B = its wave;
     // s = the chunk's T bits below the top two
-    auto pass_write = [&](auto Cc) {
-      constexpr int c = decltype(Cc)::value;
+    auto pass_write_part = [&](auto Cc, auto K0c, auto K1c) {
+      constexpr int c = decltype(Cc)::value, K0 = decltype(K0c)::value, K1 = decltype(K1c)::value;
+      if constexpr (kYStore) {
+        // (SPLITR_YCHAIN 2) the lane holds y of lane t ^ shift: x to its own slot, y to that lane's - the last hop of the chain
+        constexpr unsigned S = SplitYPlan<ND, 1>::final_shift;
+        double* __restrict__ px = reinterpret_cast<double*>(pbuf + (c & 1) * (NT * CH) + t);
+        double* __restrict__ py = reinterpret_cast<double*>(pbuf + (c & 1) * (NT * CH) + (t ^ S)) + 1;
+        splitr_for<K0, K1>([&](auto Kc) {
+          constexpr int k = decltype(Kc)::value, kp = k & PW, ks = k >> NW;
+          px[2 * 64 * NG * (kp + NG * ks)] = xr[k | (c << (NR - 2))];
+          py[2 * 64 * NG * (kp + NG * ks)] = xi[k | (c << (NR - 2))];
+        });
+        return;
+      }
       cplx* __restrict__ pb = pbuf + (c & 1) * (NT * CH) + t;
-      splitr_for<0, CH>([&](auto Kc) {
+      splitr_for<K0, K1>([&](auto Kc) {
         constexpr int k = decltype(Kc)::value, kp = k & PW, ks = k >> NW;
         pb[64 * NG * (kp + NG * ks)] = make_double2(xr[k | (c << (NR - 2))], xi[k | (c << (NR - 2))]);
       });
+    };
+    auto pass_write = [&](auto Cc) { pass_write_part(Cc, splitr_c<0>{}, splitr_c<CH>{}); };
+    // pass_write(Cw), then pre(Cp).  With the y chain the stores are SPREAD over the steps of Cp's chain (scheduling fences keep
+    // them there): issued back to back behind a barrier, the stores of the 8 waves fill the LDS queue and every wave waits at
+    // its last store before it can issue the rotations that would cover them (profiles/ychain.md: SQ_WAIT_INST_LDS)
+    auto write_pre = [&](auto Cw, auto Cp) {
+      if constexpr (kYChain) {
+        pre_regs(Cp);
+        splitr_for<0, ND + 1>([&](auto Ic) {
+          constexpr int i = decltype(Ic)::value;
+          pass_write_part(Cw, splitr_c<(i * CH / (ND + 1))>{}, splitr_c<((i + 1) * CH / (ND + 1))>{});
+          __builtin_amdgcn_sched_barrier(0);
+          chain_step(Cp, Ic);
+          __builtin_amdgcn_sched_barrier(0);
+        });
+      } else {
+        pass_write(Cw);
+        pre(Cp);
+      }
     };
     auto pass_read = [&](auto Cc) {
       constexpr int c = decltype(Cc)::value;
@@ -748,22 +828,19 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
       // transposition above and pass_write(0) - and buffer 0's last cross-wave reads, pass_read(2) of the previous
       // stage, sit before that stage's last barrier)
       pre(C0{});
-      pass_write(C0{});
-      pre(C1{});
+      write_pre(C0{}, C1{});
       __syncthreads();
       pass_read(C0{});
-      pass_write(C1{});
       if (SPLITR_KWARM) {
         typedef const __attribute__((address_space(4))) unsigned* uptr_t;
         uptr_t nx = (uptr_t)(unsigned long long)(coefs + (size_t)(sg + 1 < n_stages ? sg + 1 : sg) * stage_stride);
 #pragma unroll
         for (int k = 0; k < 8; ++k) warm ^= nx[k < 7 ? 16 * k : 8 * N - 1];
       }
-      pre(C2{});
+      write_pre(C1{}, C2{});
       __syncthreads();
       pass_read(C1{});
-      pass_write(C2{});
-      pre(C3{});
+      write_pre(C2{}, C3{});
       __syncthreads();
       pass_read(C2{});
       pass_write(C3{});
