@@ -1532,24 +1532,25 @@ def _adopt_pulser_config(config: Any) -> "QutipConfig":
         return mine.with_changes(callbacks=callbacks) if callbacks else mine
 
 
-def _observe_many_route(states: Sequence[Any], fires: Sequence[bool], engine: Any, n_eigenstates: int,
-                        min_times: int | None, energy: bool = True) -> tuple[Any, int, list[int]] | None:
-    """Which states of one ``CoherentResults`` a single ``observe_many`` call serves: (store, sequence of the
-    store, positions into ``states``), or None when the per-time path serves them all.  A position qualifies when a
-    built-in occupation / correlation / energy observable fires there (``fires``) and its state is an unread
-    ``LazyState`` ket of one ``SnapshotStore`` whose tensor ``[times, sequences, dim]`` is still on the GPU, and at
-    least ``min_times`` positions must qualify (None: the path is off).  The engine is the 2-level Ising ``Engine`` of
-    one problem in sesolve mode without extra detuning terms, or a ``GeneralEngine`` (multi-level bases, XY) that
-    ``HamiltonianOperator.observe`` would serve - a ket engine of batch 1 whose ``local_dim`` (2 - 4) is the number of
-    eigenstates and whose dimension is ``local_dim ** n`` - and, when the energy moments are wanted (``energy``), one
-    without collapse operators that applies its generator through the padded site tables
-    (``GeneralEngine.apply_path()``).  Everything else - the initial state, states already read, spilled stores - keeps
-    the per-time path; the density matrices of a two-level master-equation run have ``_observe_density_many_route``."""
-    if min_times is None or engine is None or not hasattr(engine, "observe_many"):
+def _many_route(states: Sequence[Any], fires: Sequence[bool], engine: Any, n_eigenstates: int, min_times: int | None,
+                energy: bool, density: bool) -> tuple[Any, int, list[int]] | None:
+    """Which states of one ``CoherentResults`` a single ``observe_many`` (kets) or ``observe_density_many`` (``density``)
+    call of ``engine`` serves: (store, sequence of the store, positions into ``states``), or None when the per-time
+    path serves them all.  A position qualifies when a built-in occupation / correlation / energy observable fires
+    there (``fires``) and its state is an unread ``LazyState`` - a ket, or with ``density`` a density matrix - of one
+    ``SnapshotStore`` whose tensor ``[times, sequences, dim]`` / ``[times, sequences, dim, dim]`` is still on the GPU,
+    and at least ``min_times`` positions must qualify (None: the path is off).  The engine is the noiseless 2-level
+    Ising ``Engine`` of one problem in sesolve mode, without quantum jumps and extra detuning terms, or - kets only - a
+    ``GeneralEngine`` (multi-level bases, XY) that ``HamiltonianOperator.observe`` would serve: a ket engine of batch 1
+    whose ``local_dim`` (2 - 4) is the number of eigenstates and whose dimension is ``local_dim ** n`` and, when the
+    energy moments are wanted (``energy``), one without collapse operators that applies its generator through the
+    padded site tables (``GeneralEngine.apply_path()``).  Everything else - the initial state, states already read,
+    spilled stores, ``DeviceState`` results (1 GiB and more per matrix) - keeps the per-time path."""
+    if min_times is None or engine is None or not hasattr(engine, "observe_density_many" if density else "observe_many"):
         return None
     if hasattr(engine, "local_dim"):
         d = int(engine.local_dim)
-        if (getattr(engine, "is_density", False) or getattr(engine, "batch", 0) != 1 or not 2 <= d <= 4
+        if (density or getattr(engine, "is_density", False) or getattr(engine, "batch", 0) != 1 or not 2 <= d <= 4
                 or d != n_eigenstates or d ** int(engine.n) != engine.dim):
             return None
         if energy:
@@ -1564,59 +1565,39 @@ def _observe_many_route(states: Sequence[Any], fires: Sequence[bool], engine: An
         dterms = getattr(getattr(engine, "tables", None), "dterms", None)
         if dterms is not None and len(dterms):
             return None
-    store, b, dev = None, 0, None
+    tail = (engine.dim,) * (2 if density else 1)  # the axes of one state: of the store's tensor, and of a LazyState
+    store, b = None, 0
     positions: list[int] = []
     for pos, (st, f) in enumerate(zip(states, fires)):
-        if not f or not isinstance(st, LazyState) or st._store is None or not st.isket:
+        if not f or not isinstance(st, LazyState) or st._store is None or st.isket == density:
             continue
         if store is None:
             dev = st._store.device_tensor
-            if (dev is None or not getattr(dev, "is_cuda", False) or getattr(dev, "dim", lambda: 0)() != 3
-                    or int(dev.shape[2]) != engine.dim):
+            if (dev is None or not getattr(dev, "is_cuda", False) or getattr(dev, "dim", lambda: 0)() != 2 + len(tail)
+                    or tuple(int(x) for x in dev.shape[2:]) != tail):
                 continue
             store, b = st._store, st._b
-        if st._store is store and st._b == b and st.shape[0] == engine.dim:
+        if st._store is store and st._b == b and st.shape[:len(tail)] == tail:
             positions.append(pos)
     if store is None or len(positions) < max(int(min_times), 1):
         return None
     return store, b, positions
 
 
+def _observe_many_route(states: Sequence[Any], fires: Sequence[bool], engine: Any, n_eigenstates: int,
+                        min_times: int | None, energy: bool = True) -> tuple[Any, int, list[int]] | None:
+    """``_many_route`` for the kets of a run without collapse operators (``Engine.observe_many``,
+    ``GeneralEngine.observe_many``); the caller applies ``QutipBackendV2._GENERAL_OBSERVE_MANY_FLOOR``."""
+    return _many_route(states, fires, engine, n_eigenstates, min_times, energy, density=False)
+
+
 def _observe_density_many_route(states: Sequence[Any], fires: Sequence[bool], engine: Any, n_eigenstates: int,
                                 min_times: int | None) -> tuple[Any, int, list[int]] | None:
-    """The sibling of ``_observe_many_route`` for two-level master-equation runs: which density matrices of one
-    ``CoherentResults`` a single ``Engine.observe_density_many`` call serves, as (store, sequence of the store,
-    positions into ``states``), or None when the per-time path serves them all.  A position qualifies when a built-in
-    occupation / correlation / energy observable fires there (``fires``) and its state is an unread non-ket
-    ``LazyState`` of one ``SnapshotStore`` whose tensor ``[times, sequences, dim, dim]`` is still on the GPU.  At least
-    ``max(min_times, QutipBackendV2._DENSITY_OBSERVE_MANY_FLOOR)`` positions must qualify (None: the path is off).  The
-    engine is the noiseless 2-level Ising ``Engine`` of one problem in sesolve mode, without quantum jumps and extra
-    detuning terms.  Everything else - the initial state, states already read, spilled stores, ``DeviceState`` results
-    (1 GiB and more per matrix), general engines - keeps the per-time path."""
-    if (min_times is None or engine is None or hasattr(engine, "local_dim")
-            or not hasattr(engine, "observe_density_many") or n_eigenstates != 2):
-        return None
-    if getattr(engine, "batch", 0) != 1 or getattr(engine, "mode", None) != 0 or getattr(engine, "monte_carlo", False):
-        return None  # (mode 0 = RYD_SESOLVE)
-    dterms = getattr(getattr(engine, "tables", None), "dterms", None)
-    if dterms is not None and len(dterms):
-        return None
-    store, b = None, 0
-    positions: list[int] = []
-    for pos, (st, f) in enumerate(zip(states, fires)):
-        if not f or not isinstance(st, LazyState) or st._store is None or st.isket:
-            continue
-        if store is None:
-            dev = st._store.device_tensor
-            if (dev is None or not getattr(dev, "is_cuda", False) or getattr(dev, "dim", lambda: 0)() != 4
-                    or int(dev.shape[2]) != engine.dim or int(dev.shape[3]) != engine.dim):
-                continue
-            store, b = st._store, st._b
-        if st._store is store and st._b == b and tuple(st.shape) == (engine.dim, engine.dim):
-            positions.append(pos)
-    if store is None or len(positions) < max(int(min_times), QutipBackendV2._DENSITY_OBSERVE_MANY_FLOOR):
-        return None
-    return store, b, positions
+    """``_many_route`` for the density matrices of a two-level master-equation run (``Engine.observe_density_many``), from
+    ``max(min_times, QutipBackendV2._DENSITY_OBSERVE_MANY_FLOOR)`` qualifying positions on."""
+    if min_times is not None:
+        min_times = max(int(min_times), QutipBackendV2._DENSITY_OBSERVE_MANY_FLOOR)
+    return _many_route(states, fires, engine, n_eigenstates, min_times, False, density=True)
 
 
 # ------------------------------------------------------------------- backend

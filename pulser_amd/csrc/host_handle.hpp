@@ -184,9 +184,10 @@ struct ryd_handle {
   cplx* gen_obs_scratch = nullptr;
   size_t gen_obs_scratch_bytes = 0;
   bool gen_obs_small_chunks = false;  // test hook: 5 columns per chunk
-  // ryd_observe_many / ryd_observe_density_many: [n_times] ObsManyTime, then the coefficient table [n_times][B][N][4] (grown on demand), and the
-  // pinned host copy of the former with the event that says its last upload has been read.  ryd_general_observe_many (a
-  // general handle never takes the two-level call): the same record list, then tcoef[n_terms] and mvals[E + Dg] per time
+  // The scratch of ryd_observe_many, ryd_observe_density_many and ryd_general_observe_many (obs_many_stage_times), grown
+  // on demand: [n_times] ObsManyTime, then the caller's table, and the pinned host copy of the former with the event that
+  // says its last upload has been read.  Table of the two Ising calls: coefficients [n_times][B][N][4]; of the general
+  // call (a general handle never takes the other two): tcoef[n_terms] and mvals[E + Dg] per time
   void* obs_many_dev = nullptr;
   size_t obs_many_bytes = 0;
   ObsManyTime* obs_many_pin = nullptr;

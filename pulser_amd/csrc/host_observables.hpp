@@ -214,104 +214,112 @@ static int obs_many_coef_table(ryd_handle* h, int n_times, const double* times, 
   return RYD_OK;
 }
 
-// ryd_observe for every evaluation time of a run (two-level Ising kets): the second half of k_observe.hpp
-extern "C" int ryd_observe_many(ryd_handle* h, const void* states_dev, int32_t n_times, int32_t n_batch,
-                                int64_t stride_t, int64_t stride_b, const double* times, int32_t what,
-                                double* out_dev, void* stream) {
-  if (!h) return fail(RYD_ERR_INVALID, "null handle");
-  if (h->general) return fail(RYD_ERR_INVALID, "observe_many: not available on a general-path handle");
-  int rc = check_ready(h);
-  if (rc) return rc;
-  if (h->cfg.mode != RYD_SESOLVE || h->mc)
-    return fail(RYD_ERR_UNSUPPORTED, "observe_many: kets of a sesolve handle without collapse operators only");
-  if (what & RYD_OBS_DENSITY) return fail(RYD_ERR_UNSUPPORTED, "observe_many: RYD_OBS_DENSITY is not served (use ryd_observe)");
-  if (!h->dterms_host.empty())
-    return fail(RYD_ERR_UNSUPPORTED, "observe_many: handles with extra detuning terms are not served (use ryd_observe)");
-  const int N = h->N, B = h->B;
-  const int64_t D = (int64_t)1 << N;
-  if (n_times < 0 || n_batch < 1) return fail(RYD_ERR_INVALID, "observe_many: %d times, batch %d", n_times, n_batch);
-  if (B != n_batch && B != 1)
-    return fail(RYD_ERR_INVALID, "observe_many: a handle of batch %d cannot observe %d states per time (its batch or 1)", B, n_batch);
-  if (stride_t < D || stride_b < D)
-    return fail(RYD_ERR_INVALID, "observe_many: strides %lld / %lld are smaller than a ket of %lld amplitudes",
-                (long long)stride_t, (long long)stride_b, (long long)D);
+// What the three *_many calls share once the handle is known to be theirs.  obs_many_front refuses the shapes (`who`
+// opens every message; one state is a ket of D amplitudes or, with `dm`, a matrix of D * D elements; an Ising handle of
+// batch B serves B states per time, or any number when B is 1), answers RYD_OK with n_states == 0 to a call without
+// times, zeroes the output [n_states][N*N+N+3] on the caller's stream and settles the pair kernel's launch.  A
+// general-path handle asked for the energy moments meets its two refusals here too, where they always stood: after the
+// shapes when it has collapse operators, after the device is set when it lacks the padded site tables (built there).
+struct ObsManyFront {
+  hipStream_t st;
+  int stride;          // N*N + N + 3 doubles per state
+  long long n_states;  // n_times * n_batch
+  unsigned gy;         // gridDim.y of every kernel: the states, grid-strided beyond 65535
+  bool pairs;          // the pair kernel runs and brings the norm / trace; else the energy kernel of an energy-only call does
+};
+
+static int obs_many_front(ryd_handle* h, const char* who, bool dm, int64_t D, int N, int32_t n_times, int32_t n_batch,
+                          int64_t stride_t, int64_t stride_b, const void* states_dev, const double* times, int32_t what,
+                          double* out_dev, void* stream, ObsManyFront* f) {
+  const bool gen_energy = h->general && (what & RYD_OBS_ENERGY);
+  const int64_t elems = dm ? D * D : D;
+  f->n_states = 0;
+  if (n_times < 0 || n_batch < 1) return fail(RYD_ERR_INVALID, "%s: %d times, batch %d", who, n_times, n_batch);
+  if (!h->general && h->B != n_batch && h->B != 1)
+    return fail(RYD_ERR_INVALID, "%s: a handle of batch %d cannot observe %d states per time (its batch or 1)", who, h->B, n_batch);
+  if (stride_t < elems || stride_b < elems)
+    return fail(RYD_ERR_INVALID, "%s: strides %lld / %lld are smaller than a %s of %lld %s", who, (long long)stride_t,
+                (long long)stride_b, dm ? "density matrix" : "ket", (long long)elems, dm ? "elements" : "amplitudes");
+  if (gen_energy && h->gen_mc_term >= 0)
+    return fail(RYD_ERR_UNSUPPORTED, "%s: energy moments need a handle without collapse operators (its generator is H_eff); ryd_general_observe says the same, ask for the pair sums only", who);
   if (n_times == 0) return RYD_OK;
   if (!states_dev || !times || !out_dev) return fail(RYD_ERR_INVALID, "null argument");
   HIPCHK(hipSetDevice(h->cfg.device));
-  hipStream_t st = (hipStream_t)stream;
-  const int stride = N * N + N + 3;
-  const long long n_states = (long long)n_times * n_batch;
-  HIPCHK(hipMemsetAsync(out_dev, 0, (size_t)n_states * stride * sizeof(double), st));
-  const unsigned gy = (unsigned)std::min<long long>(n_states, 65535);
-  const bool pairs = (what & (RYD_OBS_OCCUPATION | RYD_OBS_CORRELATION)) || !(what & RYD_OBS_ENERGY);
-  if (pairs) {
-    hipLaunchKernelGGL(k_obs_pairs, dim3((unsigned)((D + 2047) / 2048), gy), dim3(256), 0, st, (const cplx*)states_dev,
-                       n_states, (int)n_batch, (long long)stride_t, (long long)stride_b, N, 0, (int)what, out_dev, stride);
+  if (gen_energy) {
+    int rc;
+    if (!h->gen_sites_valid && (rc = gen_build_sites(h))) return rc;
+    if (!h->gen_fused_ok)
+      return fail(RYD_ERR_UNSUPPORTED, "%s: energy moments need the padded site tables (k_gen_apply_fused); this handle applies its generator another way: use ryd_general_observe per time", who);
+  }
+  f->st = (hipStream_t)stream;
+  f->stride = N * N + N + 3;
+  f->n_states = (long long)n_times * n_batch;
+  HIPCHK(hipMemsetAsync(out_dev, 0, (size_t)f->n_states * f->stride * sizeof(double), f->st));
+  f->gy = (unsigned)std::min<long long>(f->n_states, 65535);
+  f->pairs = (what & (RYD_OBS_OCCUPATION | RYD_OBS_CORRELATION)) || !(what & RYD_OBS_ENERGY);
+  return RYD_OK;
+}
+
+// ryd_observe for every evaluation time of a run of a two-level Ising handle (the second half of k_observe.hpp): the kets
+// of a sesolve run or, with `dm`, the density matrices of a master-equation run (ryd_observe + RYD_OBS_DENSITY).
+// k_obs_pairs on the amplitudes / the diagonals, k_eval_coefs_many, k_obs_energy_many / k_obs_energy_dm_many.
+static int ising_observe_many(ryd_handle* h, bool dm, const void* states_dev, int32_t n_times, int32_t n_batch,
+                              int64_t stride_t, int64_t stride_b, const double* times, int32_t what, double* out_dev,
+                              void* stream) {
+  const char* who = dm ? "observe_density_many" : "observe_many";
+  if (!h) return fail(RYD_ERR_INVALID, "null handle");
+  if (h->general) return fail(RYD_ERR_INVALID, "%s: not available on a general-path handle", who);
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (dm) {
+    if (h->mc) return fail(RYD_ERR_UNSUPPORTED, "observe_density_many: Monte-Carlo handles are not served (use ryd_observe)");
+  } else {
+    if (h->cfg.mode != RYD_SESOLVE || h->mc)
+      return fail(RYD_ERR_UNSUPPORTED, "observe_many: kets of a sesolve handle without collapse operators only");
+    if (what & RYD_OBS_DENSITY) return fail(RYD_ERR_UNSUPPORTED, "observe_many: RYD_OBS_DENSITY is not served (use ryd_observe)");
+  }
+  if (!h->dterms_host.empty())
+    return fail(RYD_ERR_UNSUPPORTED, "%s: handles with extra detuning terms are not served (use ryd_observe)", who);
+  const int N = h->N;
+  if (dm && 2 * N > RYD_MAX_QUBITS) return fail(RYD_ERR_INVALID, "2N exceeds %d", RYD_MAX_QUBITS);
+  const int64_t D = (int64_t)1 << N;
+  ObsManyFront f;
+  rc = obs_many_front(h, who, dm, D, N, n_times, n_batch, stride_t, stride_b, states_dev, times, what, out_dev, stream, &f);
+  if (rc || !f.n_states) return rc;
+  if (f.pairs) {
+    hipLaunchKernelGGL(k_obs_pairs, dim3((unsigned)((D + 2047) / 2048), f.gy), dim3(256), 0, f.st, (const cplx*)states_dev,
+                       f.n_states, (int)n_batch, (long long)stride_t, (long long)stride_b, N, dm ? 1 : 0, (int)what, out_dev,
+                       f.stride);
     HIPCHK(hipGetLastError());
     h->stats.n_launches++;
   }
   if (!(what & RYD_OBS_ENERGY)) return RYD_OK;
   // the (interval, offset) of every time on the host, the table of every time in one launch
   double* table = nullptr;
-  if ((rc = obs_many_coef_table(h, n_times, times, st, &table))) return rc;
-  const unsigned gx = (unsigned)std::max<int64_t>(D >> kObsManyTB, 1);
-  hipLaunchKernelGGL(k_obs_energy_many, dim3(gx, gy), dim3(256), 0, st, (const cplx*)states_dev, n_states, (int)n_batch,
-                     (long long)stride_t, (long long)stride_b, N, (const double*)table, B, (const double*)h->e0_dev,
-                     h->e0_mats == 1 ? 0ll : (long long)D, pairs ? 0 : 1, out_dev, stride);
+  if ((rc = obs_many_coef_table(h, n_times, times, f.st, &table))) return rc;
+  // kets: 2^kObsManyTB amplitudes per workgroup.  Matrices: a workgroup takes 32 rows at a time, 256 rows where there are that many
+  const unsigned gx = dm ? (unsigned)std::min<int64_t>(std::max<int64_t>(D >> 8, 1), 1024)
+                         : (unsigned)std::max<int64_t>(D >> kObsManyTB, 1);
+  const auto energy_kernel = dm ? k_obs_energy_dm_many : k_obs_energy_many;  // (one argument list serves both)
+  hipLaunchKernelGGL(energy_kernel, dim3(gx, f.gy), dim3(256), 0, f.st,
+                     (const cplx*)states_dev, f.n_states, (int)n_batch, (long long)stride_t, (long long)stride_b, N,
+                     (const double*)table, h->B, (const double*)h->e0_dev, h->e0_mats == 1 ? 0ll : (long long)D,
+                     f.pairs ? 0 : 1, out_dev, f.stride);
   HIPCHK(hipGetLastError());
   h->stats.n_launches++;
   return RYD_OK;
 }
 
-// ryd_observe + RYD_OBS_DENSITY for every density matrix of a master-equation run: k_obs_pairs on the diagonals,
-// k_eval_coefs_many, k_obs_energy_dm_many (the end of k_observe.hpp)
+extern "C" int ryd_observe_many(ryd_handle* h, const void* states_dev, int32_t n_times, int32_t n_batch,
+                                int64_t stride_t, int64_t stride_b, const double* times, int32_t what,
+                                double* out_dev, void* stream) {
+  return ising_observe_many(h, false, states_dev, n_times, n_batch, stride_t, stride_b, times, what, out_dev, stream);
+}
+
 extern "C" int ryd_observe_density_many(ryd_handle* h, const void* states_dev, int32_t n_times, int32_t n_batch,
                                         int64_t stride_t, int64_t stride_b, const double* times, int32_t what,
                                         double* out_dev, void* stream) {
-  if (!h) return fail(RYD_ERR_INVALID, "null handle");
-  if (h->general) return fail(RYD_ERR_INVALID, "observe_density_many: not available on a general-path handle");
-  int rc = check_ready(h);
-  if (rc) return rc;
-  if (h->mc)
-    return fail(RYD_ERR_UNSUPPORTED, "observe_density_many: Monte-Carlo handles are not served (use ryd_observe)");
-  if (!h->dterms_host.empty())
-    return fail(RYD_ERR_UNSUPPORTED, "observe_density_many: handles with extra detuning terms are not served (use ryd_observe)");
-  const int N = h->N, B = h->B;
-  if (2 * N > RYD_MAX_QUBITS) return fail(RYD_ERR_INVALID, "2N exceeds %d", RYD_MAX_QUBITS);
-  const int64_t D = (int64_t)1 << N;
-  if (n_times < 0 || n_batch < 1) return fail(RYD_ERR_INVALID, "observe_density_many: %d times, batch %d", n_times, n_batch);
-  if (B != n_batch && B != 1)
-    return fail(RYD_ERR_INVALID, "observe_density_many: a handle of batch %d cannot observe %d states per time (its batch or 1)", B, n_batch);
-  if (stride_t < D * D || stride_b < D * D)
-    return fail(RYD_ERR_INVALID, "observe_density_many: strides %lld / %lld are smaller than a density matrix of %lld elements",
-                (long long)stride_t, (long long)stride_b, (long long)(D * D));
-  if (n_times == 0) return RYD_OK;
-  if (!states_dev || !times || !out_dev) return fail(RYD_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  hipStream_t st = (hipStream_t)stream;
-  const int stride = N * N + N + 3;
-  const long long n_states = (long long)n_times * n_batch;
-  HIPCHK(hipMemsetAsync(out_dev, 0, (size_t)n_states * stride * sizeof(double), st));
-  const unsigned gy = (unsigned)std::min<long long>(n_states, 65535);
-  // (the trace comes with the pair kernel, or with the energy kernel of an energy-only call)
-  const bool pairs = (what & (RYD_OBS_OCCUPATION | RYD_OBS_CORRELATION)) || !(what & RYD_OBS_ENERGY);
-  if (pairs) {
-    hipLaunchKernelGGL(k_obs_pairs, dim3((unsigned)((D + 2047) / 2048), gy), dim3(256), 0, st, (const cplx*)states_dev,
-                       n_states, (int)n_batch, (long long)stride_t, (long long)stride_b, N, 1, (int)what, out_dev, stride);
-    HIPCHK(hipGetLastError());
-    h->stats.n_launches++;
-  }
-  if (!(what & RYD_OBS_ENERGY)) return RYD_OK;
-  double* table = nullptr;
-  if ((rc = obs_many_coef_table(h, n_times, times, st, &table))) return rc;
-  // a workgroup takes 32 rows at a time; 256 rows per workgroup where the matrix has that many
-  const unsigned gx = (unsigned)std::min<int64_t>(std::max<int64_t>(D >> 8, 1), 1024);
-  hipLaunchKernelGGL(k_obs_energy_dm_many, dim3(gx, gy), dim3(256), 0, st, (const cplx*)states_dev, n_states, (int)n_batch,
-                     (long long)stride_t, (long long)stride_b, N, (const double*)table, B, (const double*)h->e0_dev,
-                     h->e0_mats == 1 ? 0ll : (long long)D, pairs ? 0 : 1, out_dev, stride);
-  HIPCHK(hipGetLastError());
-  h->stats.n_launches++;
-  return RYD_OK;
+  return ising_observe_many(h, true, states_dev, n_times, n_batch, stride_t, stride_b, times, what, out_dev, stream);
 }
 
 // ryd_general_observe for every evaluation time of a run (kets of a general-path handle): k_gen_obs_pairs,
@@ -337,35 +345,21 @@ extern "C" int ryd_general_observe_many(ryd_handle* h, const void* states_dev, i
   }
   if ((int64_t)h->dim != D)
     return fail(RYD_ERR_INVALID, "general observe_many: dim %lld is not %d^%d", (long long)h->dim, local_dim, n_atoms);
-  if (n_times < 0 || n_batch < 1) return fail(RYD_ERR_INVALID, "general observe_many: %d times, batch %d", n_times, n_batch);
-  if (stride_t < D || stride_b < D)
-    return fail(RYD_ERR_INVALID, "general observe_many: strides %lld / %lld are smaller than a ket of %lld amplitudes",
-                (long long)stride_t, (long long)stride_b, (long long)D);
-  const bool energy = (what & RYD_OBS_ENERGY) != 0;
-  if (energy && h->gen_mc_term >= 0)
-    return fail(RYD_ERR_UNSUPPORTED, "general observe_many: energy moments need a handle without collapse operators (its generator is H_eff); ryd_general_observe says the same, ask for the pair sums only");
-  if (n_times == 0) return RYD_OK;
-  if (!states_dev || !times || !out_dev) return fail(RYD_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  hipStream_t st = (hipStream_t)stream;
-  if (energy) {
-    if (!h->gen_sites_valid && (rc = gen_build_sites(h))) return rc;
-    if (!h->gen_fused_ok)
-      return fail(RYD_ERR_UNSUPPORTED, "general observe_many: energy moments need the padded site tables (k_gen_apply_fused); this handle applies its generator another way: use ryd_general_observe per time");
-  }
   const int N = n_atoms;
-  const int stride = N * N + N + 3;
-  const long long n_states = (long long)n_times * n_batch;
-  HIPCHK(hipMemsetAsync(out_dev, 0, (size_t)n_states * stride * sizeof(double), st));
-  const bool pairs = (what & (RYD_OBS_OCCUPATION | RYD_OBS_CORRELATION)) || !energy;
-  if (pairs) {
-    hipLaunchKernelGGL(k_gen_obs_pairs, dim3((unsigned)((D + 2047) / 2048), (unsigned)std::min<long long>(n_states, 65535)),
-                       dim3(256), 0, st, (const cplx*)states_dev, n_states, (int)n_batch, (long long)stride_t,
-                       (long long)stride_b, (unsigned)D, N, (int)local_dim, (int)one_digit, 0, (int)what, out_dev, stride);
+  ObsManyFront f;
+  rc = obs_many_front(h, "general observe_many", false, D, N, n_times, n_batch, stride_t, stride_b, states_dev, times, what,
+                      out_dev, stream, &f);
+  if (rc || !f.n_states) return rc;
+  const hipStream_t st = f.st;
+  const int stride = f.stride;
+  if (f.pairs) {
+    hipLaunchKernelGGL(k_gen_obs_pairs, dim3((unsigned)((D + 2047) / 2048), f.gy), dim3(256), 0, st,
+                       (const cplx*)states_dev, f.n_states, (int)n_batch, (long long)stride_t, (long long)stride_b,
+                       (unsigned)D, N, (int)local_dim, (int)one_digit, 0, (int)what, out_dev, stride);
     HIPCHK(hipGetLastError());
     h->stats.n_launches++;
   }
-  if (!energy) return RYD_OK;
+  if (!(what & RYD_OBS_ENERGY)) return RYD_OK;
   // (interval, offset) of every time on the host; per time tcoef[n_terms] and mvals[E + Dg] in the handle's scratch (the
   // handle's own gen_tcoef / gen_fused.mvals / wA are not written).  Calls on one handle are ordered by using ONE stream.
   const GenFusedDev& F = h->gen_fused;
@@ -403,7 +397,7 @@ extern "C" int ryd_general_observe_many(ryd_handle* h, const void* states_dev, i
   A.n_diag = h->gen_n_diag;
   A.d = h->gen_d;
   A.n_dig = h->gen_ndig;
-  A.with_norm = pairs ? 0 : 1;
+  A.with_norm = f.pairs ? 0 : 1;
   A.out_stride = stride;
   A.off = N * N + N + 1;
   A.norm_off = N;

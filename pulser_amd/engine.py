@@ -53,6 +53,32 @@ def _obs_unpack(out: Any, n: int) -> dict[str, np.ndarray]:
             "energy": o[..., n * n + n + 1], "energy2": o[..., n * n + n + 2]}
 
 
+def _many_args(torch: Any, device: Any, states: Any, times: Any,
+               tail: tuple[int, ...]) -> tuple[int, int, int, int, np.ndarray]:
+    """The arguments the ``*_many`` observe calls share.  ``states`` is a complex128 tensor ``[T, B >= 1, *tail]`` on
+    ``device`` whose trailing axes are contiguous (the first two may be strided); ``tail`` is ``(dim,)`` for kets and
+    ``(d, d)`` for density matrices.  ``times`` has one entry per state of the first axis.  Returns T, B, the strides
+    of the first two axes in elements and ``times`` as a contiguous float64 array."""
+    if not (isinstance(states, torch.Tensor) and states.is_cuda and states.device == device):
+        raise ValueError(f"states must be a torch tensor on {device}")
+    if states.dtype != torch.complex128:
+        raise ValueError(f"states must be complex128, got {states.dtype}")
+    if states.dim() != 2 + len(tail) or tuple(states.shape[2:]) != tail or int(states.shape[1]) < 1:
+        raise ValueError(f"states must have the shape [T, B >= 1, {', '.join(map(str, tail))}], got {tuple(states.shape)}")
+    if states.stride(-1) != 1 or (len(tail) == 2 and states.stride(2) != tail[1]):
+        raise ValueError(f"the last {'axis' if len(tail) == 1 else 'two axes'} of states must be contiguous"
+                         " (the first two may be strided)")
+    n_t, n_b = int(states.shape[0]), int(states.shape[1])
+    tt = np.ascontiguousarray(times, dtype=np.float64)
+    if tt.shape != (n_t,):
+        raise ValueError(f"need one time per state of the first axis ({n_t}), got {tt.shape}")
+    # (the stride of an axis of length 1 is arbitrary in torch and never used: any valid value will do)
+    elems = int(np.prod(tail))
+    stride_b = int(states.stride(1)) if n_b > 1 else elems
+    stride_t = int(states.stride(0)) if n_t > 1 else max(n_b * stride_b, elems)
+    return n_t, n_b, stride_t, stride_b, tt
+
+
 def outer_accumulate(psi: Any, acc: Any, weights: Any = None) -> None:
     """``acc[D, D] += sum_b w_b |psi_b><psi_b|`` on the device, without a solver handle and for any
     state dimension (``ryd_outer_accumulate_dim``): the trajectory mean of
@@ -562,21 +588,7 @@ class Engine:
         arrays ``norm2`` [T, B], ``occupation`` [T, B, N], ``correlation`` [T, B, N, N], ``energy`` [T, B],
         ``energy2`` [T, B] - NOT normalised (divide by ``norm2``); what was not asked for is 0."""
         torch = self.torch
-        if not (isinstance(states, torch.Tensor) and states.is_cuda and states.device == self.device):
-            raise ValueError(f"states must be a torch tensor on {self.device}")
-        if states.dtype != torch.complex128:
-            raise ValueError(f"states must be complex128, got {states.dtype}")
-        if states.dim() != 3 or int(states.shape[2]) != self.dim or int(states.shape[1]) < 1:
-            raise ValueError(f"states must have the shape [T, B >= 1, {self.dim}], got {tuple(states.shape)}")
-        if states.stride(2) != 1:
-            raise ValueError("the last axis of states must be contiguous (the first two may be strided)")
-        n_t, n_b = int(states.shape[0]), int(states.shape[1])
-        tt = np.ascontiguousarray(times, dtype=np.float64)
-        if tt.shape != (n_t,):
-            raise ValueError(f"need one time per state of the first axis ({n_t}), got {tt.shape}")
-        # (the stride of an axis of length 1 is arbitrary in torch and never used: any valid value will do)
-        stride_b = int(states.stride(1)) if n_b > 1 else self.dim
-        stride_t = int(states.stride(0)) if n_t > 1 else max(n_b * stride_b, self.dim)
+        n_t, n_b, stride_t, stride_b, tt = _many_args(torch, self.device, states, times, (self.dim,))
         n = self.n
         what = _obs_what(occupation, correlation, energy)
         out = torch.empty((n_t, n_b, n * n + n + 3), dtype=torch.float64, device=self.device)
@@ -598,21 +610,7 @@ class Engine:
         normalised (divide by ``norm2``); what was not asked for is 0."""
         torch = self.torch
         d = 1 << self.n
-        if not (isinstance(states, torch.Tensor) and states.is_cuda and states.device == self.device):
-            raise ValueError(f"states must be a torch tensor on {self.device}")
-        if states.dtype != torch.complex128:
-            raise ValueError(f"states must be complex128, got {states.dtype}")
-        if states.dim() != 4 or tuple(states.shape[2:]) != (d, d) or int(states.shape[1]) < 1:
-            raise ValueError(f"states must have the shape [T, B >= 1, {d}, {d}], got {tuple(states.shape)}")
-        if states.stride(3) != 1 or states.stride(2) != d:
-            raise ValueError("the last two axes of states must be contiguous (the first two may be strided)")
-        n_t, n_b = int(states.shape[0]), int(states.shape[1])
-        tt = np.ascontiguousarray(times, dtype=np.float64)
-        if tt.shape != (n_t,):
-            raise ValueError(f"need one time per state of the first axis ({n_t}), got {tt.shape}")
-        # (the stride of an axis of length 1 is arbitrary in torch and never used: any valid value will do)
-        stride_b = int(states.stride(1)) if n_b > 1 else d * d
-        stride_t = int(states.stride(0)) if n_t > 1 else max(n_b * stride_b, d * d)
+        n_t, n_b, stride_t, stride_b, tt = _many_args(torch, self.device, states, times, (d, d))
         n = self.n
         what = _obs_what(occupation, correlation, energy)
         out = torch.empty((n_t, n_b, n * n + n + 3), dtype=torch.float64, device=self.device)
@@ -953,21 +951,7 @@ class GeneralEngine:
             raise ValueError(f"'one' must be a digit in [0, {self.local_dim}), got {one}")
         if not 2 <= self.local_dim <= 4:
             raise ValueError(f"observe_many takes local dimensions 2 - 4, got {self.local_dim}")
-        if not (isinstance(states, torch.Tensor) and states.is_cuda and states.device == self.device):
-            raise ValueError(f"states must be a torch tensor on {self.device}")
-        if states.dtype != torch.complex128:
-            raise ValueError(f"states must be complex128, got {states.dtype}")
-        if states.dim() != 3 or int(states.shape[2]) != self.dim or int(states.shape[1]) < 1:
-            raise ValueError(f"states must have the shape [T, B >= 1, {self.dim}], got {tuple(states.shape)}")
-        if states.stride(2) != 1:
-            raise ValueError("the last axis of states must be contiguous (the first two may be strided)")
-        n_t, n_b = int(states.shape[0]), int(states.shape[1])
-        tt = np.ascontiguousarray(times, dtype=np.float64)
-        if tt.shape != (n_t,):
-            raise ValueError(f"need one time per state of the first axis ({n_t}), got {tt.shape}")
-        # (the stride of an axis of length 1 is arbitrary in torch and never used: any valid value will do)
-        stride_b = int(states.stride(1)) if n_b > 1 else self.dim
-        stride_t = int(states.stride(0)) if n_t > 1 else max(n_b * stride_b, self.dim)
+        n_t, n_b, stride_t, stride_b, tt = _many_args(torch, self.device, states, times, (self.dim,))
         n = self.n
         what = _obs_what(occupation, correlation, energy)
         out = torch.empty((n_t, n_b, n * n + n + 3), dtype=torch.float64, device=self.device)
