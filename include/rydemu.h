@@ -558,6 +558,24 @@ int ryd_expect_sparse(const void* states_dev, int64_t n_states, int64_t stride, 
                       int32_t density, const int32_t* rows_dev, const int32_t* cols_dev,
                       const void* vals_dev, int64_t nnz, void* out_dev, int32_t device, void* stream);
 
+/* Replaces: Fidelity's QutipState.overlap at every evaluation time (pulser_simulation/qutip_state.py:86-110) and the
+ * normalisation of every state (Qobj.unit) for the states that are still device snapshots.
+ * z[s][f] = sum_i conj(a_f[i]) x_s[i]   and   nrm[s]   for every stored state s and target f: one memset per output
+ * (out_dev, norm_dev) and one launch.
+ *   density = 0: x_s kets complex128[dim];  nrm[s] = sum |x_s[i]|^2;  target_form must be 0 (a_f: complex128[dim]).
+ *   density = 1: x_s row-major dim x dim;   nrm[s] = Re Tr x_s;
+ *       target_form 0: a_f complex128[dim*dim] (a density-matrix target: z = Tr(A^dag rho));
+ *       target_form 1: a_f = phi_f complex128[dim], used as A = |phi><phi| formed on the fly:
+ *                      z = sum_ij conj(phi_i) phi_j rho_ij = <phi|rho|phi>;  A is never materialised.
+ * state s starts at states_dev + s*stride (complex128 elements, 64-bit offsets; stride >= dim or dim*dim, else
+ * RYD_ERR_INVALID).  targets_dev is contiguous [n_targets][len].  out_dev complex128[n_states][n_targets],
+ * norm_dev float64[n_states]; both overwritten.  n_targets = 0 is valid (norms only; targets_dev / out_dev may be null);
+ * n_states = 0 returns RYD_OK and launches nothing.  density = 0 with target_form = 1, negative counts, dim < 1,
+ * null pointers that are needed: RYD_ERR_INVALID.  No host synchronisation. */
+int ryd_overlap_many(const void* states_dev, int64_t n_states, int64_t stride, int64_t dim, int32_t density,
+                     const void* targets_dev, int32_t n_targets, int32_t target_form,
+                     void* out_dev, double* norm_dev, int32_t device, void* stream);
+
 int ryd_get_stats(const ryd_handle* h, ryd_stats* out);
 int ryd_reset_stats(ryd_handle* h);
 

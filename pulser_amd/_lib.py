@@ -141,6 +141,8 @@ SYMBOLS = {
     "ryd_accumulate": (C.c_int, [C.c_void_p, C.c_double, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
     "ryd_expect_sparse": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
+    "ryd_overlap_many": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                   C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "ryd_replay_samples": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_double, C.c_double, C.c_void_p, C.c_int32]),

@@ -64,6 +64,9 @@ def _validate_shape(shape: tuple[int, ...], qudit_dim: int) -> None:
         )
 
 
+_UNSEEDED = object()  # RydState.seeded_value: nothing was computed for this observable
+
+
 # ------------------------------------------------------------------- state
 class RydState:
     """``QutipState`` (pulser_simulation/qutip_state.py:38-281) on a NumPy state."""
@@ -120,6 +123,11 @@ class RydState:
 
     def to_qobj(self) -> QState:
         return self._state
+
+    def seeded_value(self, observable: "Observable") -> Any:
+        """A value already computed for ``observable`` on this state, or ``_UNSEEDED``: only the deferred state of a
+        device snapshot ever carries one."""
+        return _UNSEEDED
 
     def infer_one_state(self) -> str:
         """pulser/backend/state.py: the eigenstate measured as 1."""
@@ -258,8 +266,9 @@ class _DeferredRydState(RydState):
     first access to its data.  ``eigenstates``, ``n_qudits``, ``qudit_dim`` and ``infer_one_state`` need no data, so
     an evaluation time whose observables were all served by ``Engine.observe_many`` (kets) or
     ``Engine.observe_density_many`` (density matrices: ``unit()`` divides by the trace norm) costs no device-to-host copy;
-    whoever does read the state (``StateResult``, ``BitStrings``, ``Fidelity``, ``Expectation``, a callback) gets
-    exactly the state the eager construction gives."""
+    ``Fidelity`` and ``Expectation`` return the value ``seed`` handed over for them (``engine.overlap_many``,
+    ``engine.expect_sparse``) without reading it either.  Whoever does read the state (``StateResult``, ``BitStrings``,
+    a callback, an observable without a seeded value) gets exactly the state the eager construction gives."""
 
     def __init__(self, lazy: Any, *, eigenstates: Sequence[str]) -> None:
         _validate_eigenstates(eigenstates)
@@ -270,6 +279,9 @@ class _DeferredRydState(RydState):
         self._amplitudes = None
         self._lazy = lazy
         self._q: QState | None = None
+        # uuid of a Fidelity / Expectation -> the value ``engine.overlap_many`` / ``engine.expect_sparse`` computed for
+        # this state on the device (``QutipBackendV2._overlap_many_route``): that observable's ``apply`` returns it
+        self._seeded: dict[Any, Any] = {}
 
     @property
     def _state(self) -> QState:  # type: ignore[override]
@@ -277,6 +289,12 @@ class _DeferredRydState(RydState):
             self._q = QState(np.asarray(self._lazy.unit()))
             self._lazy = None
         return self._q
+
+    def seed(self, observable: "Observable", value: Any) -> None:
+        self._seeded[observable.uuid] = value
+
+    def seeded_value(self, observable: "Observable") -> Any:
+        return self._seeded.get(observable.uuid, _UNSEEDED)
 
 
 class RydOperator:
@@ -670,6 +688,9 @@ class Fidelity(Observable):
         return d
 
     def apply(self, *, state: RydState, **kw: Any) -> float:
+        seeded = state.seeded_value(self)
+        if seeded is not _UNSEEDED:  # computed on the device for this snapshot: the state is not read
+            return seeded
         return self.state.overlap(state)
 
 
@@ -697,6 +718,9 @@ class Expectation(Observable):
         return d
 
     def apply(self, *, state: RydState, **kw: Any) -> Any:
+        seeded = state.seeded_value(self)
+        if seeded is not _UNSEEDED:  # computed on the device for this snapshot: the state is not read
+            return seeded
         if isinstance(self.operator, RydOperator):
             return self.operator.expect(state)
         s = np.asarray(state.to_qobj())
@@ -1566,22 +1590,40 @@ def _many_route(states: Sequence[Any], fires: Sequence[bool], engine: Any, n_eig
         if dterms is not None and len(dterms):
             return None
     tail = (engine.dim,) * (2 if density else 1)  # the axes of one state: of the store's tensor, and of a LazyState
-    store, b = None, 0
-    positions: list[int] = []
-    for pos, (st, f) in enumerate(zip(states, fires)):
-        if not f or not isinstance(st, LazyState) or st._store is None or st.isket == density:
-            continue
-        if store is None:
-            dev = st._store.device_tensor
-            if (dev is None or not getattr(dev, "is_cuda", False) or getattr(dev, "dim", lambda: 0)() != 2 + len(tail)
-                    or tuple(int(x) for x in dev.shape[2:]) != tail):
-                continue
-            store, b = st._store, st._b
-        if st._store is store and st._b == b and st.shape[:len(tail)] == tail:
-            positions.append(pos)
+    store, b, positions, _ = _walk_store(states, fires, tail)
     if store is None or len(positions) < max(int(min_times), 1):
         return None
     return store, b, positions
+
+
+def _walk_store(states: Sequence[Any], fires: Sequence[bool],
+                tail: tuple[int, ...] | None) -> tuple[Any, int, list[int], tuple[int, ...] | None]:
+    """The store walk of the one-call routes: (store, sequence of the store, positions into ``states``, tail).  The
+    first unread ``LazyState`` at a firing position whose ``SnapshotStore`` still holds a GPU tensor
+    ``[times, sequences, *tail]`` picks the store and the sequence; the positions are the firing, unread states of
+    that store and sequence.  ``tail`` is ``(D,)`` for kets or ``(D, D)`` for density matrices; None takes either from
+    the first store that has one.  (None, 0, [], tail) when no store qualifies."""
+    store, b = None, 0
+    positions: list[int] = []
+    for pos, (st, f) in enumerate(zip(states, fires)):
+        if not f or not isinstance(st, LazyState) or st._store is None:
+            continue
+        if tail is not None and st.isket != (len(tail) == 1):
+            continue
+        if store is None:
+            dev = st._store.device_tensor
+            if dev is None or not getattr(dev, "is_cuda", False):
+                continue
+            n_axes = getattr(dev, "dim", lambda: 0)() - 2
+            if n_axes not in ((1, 2) if tail is None else (len(tail),)):
+                continue
+            found = tuple(int(x) for x in dev.shape[2:])
+            if found != ((found[0],) * n_axes if tail is None else tail) or st.isket != (n_axes == 1):
+                continue
+            store, b, tail = st._store, st._b, found
+        if st._store is store and st._b == b and st.shape[:len(tail)] == tail:
+            positions.append(pos)
+    return store, b, positions, tail
 
 
 def _observe_many_route(states: Sequence[Any], fires: Sequence[bool], engine: Any, n_eigenstates: int,
@@ -1598,6 +1640,24 @@ def _observe_density_many_route(states: Sequence[Any], fires: Sequence[bool], en
     if min_times is not None:
         min_times = max(int(min_times), QutipBackendV2._DENSITY_OBSERVE_MANY_FLOOR)
     return _many_route(states, fires, engine, n_eigenstates, min_times, False, density=True)
+
+
+def _overlap_many_route(states: Sequence[Any], fires: Sequence[bool],
+                        min_times: int | None) -> tuple[Any, int, list[int], bool] | None:
+    """Which states of one ``CoherentResults`` the device calls behind ``Fidelity`` / ``Expectation``
+    (``engine.overlap_many``, ``engine.expect_sparse``) serve: (store, sequence of the store, positions into ``states``,
+    whether the states are density matrices), or None when the per-time path serves them all.  A position qualifies
+    when one of those observables fires there (``fires``) and its state is an unread ``LazyState`` of one
+    ``SnapshotStore`` whose tensor ``[times, sequences, dim]`` or ``[times, sequences, dim, dim]`` is still on the GPU;
+    at least ``max(min_times, QutipBackendV2._OVERLAP_MANY_FLOOR)`` positions must qualify (None: the path is off).  No
+    engine is involved.  The initial state, states already read, spilled stores and ``DeviceState`` results keep the
+    per-time path."""
+    if min_times is None:
+        return None
+    store, b, positions, tail = _walk_store(states, fires, None)
+    if store is None or len(positions) < max(int(min_times), QutipBackendV2._OVERLAP_MANY_FLOOR):
+        return None
+    return store, b, positions, len(tail) == 2
 
 
 # ------------------------------------------------------------------- backend
@@ -1624,6 +1684,10 @@ class QutipBackendV2:
     # launch counts of short master-equation runs are part of what the suite pins.  (Measured,
     # profiles/observe_density_many.md: the one-call path won at every count from 128 on, so the break-even lies below it.)
     _DENSITY_OBSERVE_MANY_FLOOR = 128
+    # Fidelity and Expectation come from one engine.overlap_many call per store (and one engine.expect_sparse call per
+    # operator) from max(observe_many_min_times, this floor) evaluation times on.  (The value is carried over from the
+    # routes above and was not tuned for this one; profiles/overlap_many.md has timings at 128 and above, none below.)
+    _OVERLAP_MANY_FLOOR = 128
 
     def __init__(self, sequence: Any, *, config: QutipConfig | None = None,
                  mimic_qpu: bool = False) -> None:
@@ -1734,10 +1798,13 @@ class QutipBackendV2:
         # a ket run of the general path: a multi-level basis or XY mode (what _fast_path_ok turns away) without collapse
         # operators (sesolve).  Master-equation and quantum-jump runs, and every 2-level Ising run, are left exactly as
         # they are: no option is set and the noiseless engine is lowered as before
-        general_ket_run = (min_times is not None and bool(watching)
-                           and (hdata.basis_name not in SUPPORTED_BASES or len(hdata.eigenbasis) != 2
-                                or hdata.interaction_type == "XY")
-                           and not hdata.collapse_ops()[0])
+        def general_kets() -> bool:
+            return (min_times is not None
+                    and (hdata.basis_name not in SUPPORTED_BASES or len(hdata.eigenbasis) != 2
+                         or hdata.interaction_type == "XY")
+                    and not hdata.collapse_ops()[0])
+
+        general_ket_run = bool(watching) and general_kets()
         if general_ket_run:
             # the kets stay on the device (QutipEmulator.run(general_device_snapshots=True)) when enough evaluation times
             # carry a built-in observable for the one-call path to take them
@@ -1747,6 +1814,105 @@ class QutipBackendV2:
                 general_one_call = True
         many_cache: dict[str, Any] = {}  # the observe_many result of the LAST store seen: shared by the sequences of
         #                                  one batched solve and their repetitions, dropped with the next solve
+
+        def snapshots(dev: Any, idx: Sequence[int]) -> Any:
+            """The snapshots ``idx`` of a store's tensor: a view for every time or every k-th, else a gathered copy."""
+            step = idx[1] - idx[0] if len(idx) > 1 else 1
+            if step > 0 and all(j - i == step for i, j in zip(idx, idx[1:])):
+                return dev[idx[0]:idx[-1] + 1:step]
+            import torch
+
+            return dev[torch.as_tensor(idx, dtype=torch.long, device=dev.device)]
+
+        def overlap_form(obs: Any, dim: int | None, density: bool) -> str | None:
+            """How the device serves ``obs`` on snapshots of dimension ``dim`` (None: any): "ket" / "dm" (the kind of a
+            Fidelity's target), "op" (an Expectation), or None where the per-time path has to answer - it rejects
+            other eigenstates or sizes with its own errors, and <psi|A|psi> with a dense A is not covered."""
+            if isinstance(obs, Fidelity):
+                target = obs.state
+                if target.eigenstates != tuple(eigenstates):
+                    return None
+                q = target.to_qobj()
+                if not isinstance(q, QState) or dim not in (None, q.shape[0]):
+                    return None
+                return "ket" if q.isket else ("dm" if density else None)
+            if isinstance(obs, Expectation):
+                op = obs.operator
+                if isinstance(op, RydOperator):
+                    return "op" if op.eigenstates == tuple(eigenstates) and dim in (None, op.to_qobj().shape[0]) else None
+                return "op" if (op.ndim == 2 and op.shape[0] == op.shape[1] and dim in (None, op.shape[0])
+                                and op.dtype.kind in "biufc") else None
+            return None
+
+        # the Fidelity / Expectation observables the device may serve (the dimension, and whether a density-matrix target
+        # is served, show once the snapshots are there)
+        overlap_watchers = [o for o in config.observables if overlap_form(o, None, True) is not None]
+        on_kets = [o for o in overlap_watchers if overlap_form(o, None, False) is not None]
+        if on_kets and not options.get("general_device_snapshots") and general_kets():
+            # the kets of a multi-level / XY run stay on the device for these observables alone, too; how the noiseless
+            # engine is lowered (general_one_call) does not change
+            firing = sum(any(o._fires(config, float(t / (T * 1e-3)), T) for o in on_kets) for t in sim._eval_times_array)
+            if firing >= max(int(min_times), QutipBackendV2._OVERLAP_MANY_FLOOR):
+                options = {**options, "general_device_snapshots": True}
+        overlap_cache: dict[str, Any] = {}  # like many_cache, for overlapped_many
+
+        def overlapped_many(rs: Sequence[Any]) -> dict[int, tuple[dict[Any, np.ndarray], int, int]]:
+            """position in ``rs`` -> (finished values [row, column] by observable, its row, its column), {} on the
+            per-time path: ONE ``overlap_many`` call per store and kind of target (it brings the norms or traces; with
+            no Fidelity a call without targets does) and one ``expect_sparse`` call per operator, finished on the
+            host: |z|^2 / norm (ket on kets), Re z / trace (density matrices), e / norm or e / trace."""
+            if min_times is None or not overlap_watchers or not rs:
+                return {}
+            # only what the device serves on THIS run's snapshots counts towards the threshold: their kind and dimension
+            # are those of the first unread snapshot (a density-matrix target on kets reads every state per time anyway)
+            first = next((r.state for r in rs if isinstance(r.state, LazyState) and r.state._store is not None), None)
+            if first is None:
+                return {}
+            forms = {o.uuid: (o, overlap_form(o, int(first.shape[0]), not first.isket)) for o in overlap_watchers}
+            forms = {k: v for k, v in forms.items() if v[1] is not None}
+            if not forms:
+                return {}
+            fires = [any(o._fires(config, float(r.evaluation_time), T) for o, _ in forms.values()) for r in rs]
+            route = _overlap_many_route([r.state for r in rs], fires, min_times)
+            if route is None or route[3] == first.isket:
+                return {}
+            store, b, positions, density = route
+            idx = [rs[p].state._i for p in positions]
+            key = (tuple(idx), density)
+            if overlap_cache.get("store") is not store or overlap_cache.get("key") != key:
+                dev = store.device_tensor
+                if dev is None:  # spilled since the route was taken
+                    return {}
+                from .engine import expect_sparse, overlap_many
+
+                dim = int(dev.shape[-1])
+                if dim != int(first.shape[0]):
+                    return {}
+                x = snapshots(dev, idx)
+                n_s, n_b = int(x.shape[0]), int(x.shape[1])
+                # [times, sequences] as one axis of states: in place for one sequence or a dense block, else a copy
+                flat = x[:, 0] if n_b == 1 else x.reshape((n_s * n_b,) + tuple(x.shape[2:]))
+                norm, got = None, {}
+                for form in ("ket", "dm"):
+                    group = [o for o, f in forms.values() if f == form]
+                    if not group:
+                        continue
+                    targets = np.stack([np.asarray(o.state.to_qobj()).reshape(-1) for o in group])
+                    z, nrm = overlap_many(flat, targets, density=density, outer=density and form == "ket")
+                    norm = nrm.cpu().numpy() if norm is None else norm
+                    z = z.cpu().numpy()
+                    for k, o in enumerate(group):
+                        got[o.uuid] = (z[:, k].real / norm if density else np.abs(z[:, k]) ** 2 / norm).reshape(n_s, n_b)
+                if norm is None:
+                    norm = overlap_many(flat, np.zeros((0, dim), complex), density=density, outer=density)[1].cpu().numpy()
+                for o, f in forms.values():
+                    if f == "op":
+                        op = o.operator.to_qobj() if isinstance(o.operator, RydOperator) else o.operator
+                        got[o.uuid] = (expect_sparse(flat, op, density=density).cpu().numpy() / norm).reshape(n_s, n_b)
+                overlap_cache.clear()
+                overlap_cache.update(store=store, key=key, got=got)
+            got = overlap_cache["got"]
+            return {p: (got, row, b) for row, p in enumerate(positions)}
 
         def observed_many(rs: Sequence[Any]) -> dict[int, tuple[dict[int, dict[str, np.ndarray]], int, int]]:
             """position in ``rs`` -> (observe_many results by digit counted, its row, its column), {} on the per-time path."""
@@ -1778,13 +1944,7 @@ class QutipBackendV2:
                 dev = store.device_tensor
                 if dev is None:  # spilled since the route was taken
                     return {}
-                step = idx[1] - idx[0] if len(idx) > 1 else 1
-                if step > 0 and all(j - i == step for i, j in zip(idx, idx[1:])):
-                    x = dev[idx[0]:idx[-1] + 1:step]  # every time, or every k-th: a view, observed in place
-                else:
-                    import torch
-
-                    x = dev[torch.as_tensor(idx, dtype=torch.long, device=dev.device)]
+                x = snapshots(dev, idx)  # every time, or every k-th: a view, observed in place
                 if density:
                     got = {0: eng.observe_density_many(x, times_us, energy=wants_energy)}
                 elif hasattr(eng, "local_dim"):  # (only the first call carries the energy moments)
@@ -1800,12 +1960,19 @@ class QutipBackendV2:
         def fill(res: Results, coherent: Any) -> None:
             rs = list(coherent)
             many = observed_many(rs)
+            overlaps = overlapped_many(rs)
             for pos, r in enumerate(rs):
                 t = r.evaluation_time
                 served = many.get(pos)
-                if many and isinstance(r.state, LazyState):
-                    # the one-call path is on: a snapshot crosses PCIe when an observable or a callback reads it
+                if (many or overlaps) and isinstance(r.state, LazyState):
+                    # a one-call path is on: a snapshot crosses PCIe when an observable or a callback reads it
                     state = _DeferredRydState(r.state, eigenstates=eigenstates)
+                    if pos in overlaps:
+                        values, row, col = overlaps[pos]
+                        for o in overlap_watchers:
+                            if o.uuid in values:
+                                v = values[o.uuid][row, col]
+                                state.seed(o, float(v) if isinstance(o, Fidelity) else complex(v))
                 else:
                     state = RydState(r.state.unit(), eigenstates=eigenstates)
                 ham = HamiltonianOperator(noiseless_engine(), t * T / 1000, eigenstates, energy_expected=wants_energy)
@@ -1900,6 +2067,7 @@ class QutipBackendV2:
             QutipBackendV2.last_timing = timing
             QutipBackendV2.last_observable_engine_stats = holder[0].stats() if holder else None
             many_cache.clear()
+            overlap_cache.clear()
             for eng in holder:
                 eng.close()
 

@@ -515,6 +515,64 @@ extern "C" int ryd_expect_sparse(const void* states_dev, int64_t n_states, int64
   return RYD_OK;
 }
 
+// z[s][f] = <a_f|x_s>, Tr(A_f^dag rho_s) or <phi_f|rho_s|phi_f>, and the norm / trace of every state: k_overlap.hpp
+extern "C" int ryd_overlap_many(const void* states_dev, int64_t n_states, int64_t stride, int64_t dim, int32_t density,
+                                const void* targets_dev, int32_t n_targets, int32_t target_form, void* out_dev,
+                                double* norm_dev, int32_t device, void* stream) {
+  if (n_states < 0) return fail(RYD_ERR_INVALID, "overlap: n_states %lld is negative", (long long)n_states);
+  if (n_targets < 0) return fail(RYD_ERR_INVALID, "overlap: n_targets %d is negative", (int)n_targets);
+  // (dim * dim elements per matrix: 2^31 - 1 of them is already 32 GiB)
+  if (dim < 1 || dim > (density ? 46340 : INT32_MAX))
+    return fail(RYD_ERR_INVALID, "overlap: dim %lld outside [1, %d]", (long long)dim, density ? 46340 : INT32_MAX);
+  if (target_form != 0 && target_form != 1) return fail(RYD_ERR_INVALID, "overlap: target_form %d is not 0 or 1", (int)target_form);
+  if (target_form == 1 && !density)
+    return fail(RYD_ERR_INVALID, "overlap: target_form 1 (|phi><phi| formed on the fly) needs density = 1");
+  const int64_t len = density ? dim * dim : dim;
+  if (stride < len)
+    return fail(RYD_ERR_INVALID, "overlap: stride %lld is smaller than a %s of dim %lld", (long long)stride,
+                density ? "density matrix" : "ket", (long long)dim);
+  if (n_states == 0) return RYD_OK;
+  if (!states_dev) return fail(RYD_ERR_INVALID, "overlap: states_dev is null");
+  if (!norm_dev) return fail(RYD_ERR_INVALID, "overlap: norm_dev is null");
+  if (n_targets > 0 && !targets_dev) return fail(RYD_ERR_INVALID, "overlap: targets_dev is null with %d targets", (int)n_targets);
+  if (n_targets > 0 && !out_dev) return fail(RYD_ERR_INVALID, "overlap: out_dev is null with %d targets", (int)n_targets);
+  const int64_t n_chunks = (len + kOverlapChunk - 1) / kOverlapChunk;
+  const int tile = n_targets <= 1 ? 1 : kOverlapTile;  // a lone target (or none): a quarter of the weight registers
+  const int64_t n_tiles = std::max<int64_t>(1, ((int64_t)n_targets + tile - 1) / tile);
+  if (n_tiles > 65535) return fail(RYD_ERR_INVALID, "overlap: n_targets %d exceeds %d", (int)n_targets, 65535 * kOverlapTile);
+  HIPCHK(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipMemsetAsync(norm_dev, 0, (size_t)n_states * sizeof(double), st));
+  if (n_targets > 0) HIPCHK(hipMemsetAsync(out_dev, 0, (size_t)n_states * (size_t)n_targets * sizeof(cplx), st));
+  // a workgroup keeps its weights in registers and walks every grid.z-th state: about 4 096 workgroups in all, so that
+  // small states still fill the device and large ones amortise the weight loads over many states
+  const int64_t per_state = n_chunks * n_tiles;
+  const int64_t gz = std::min<int64_t>(std::min<int64_t>(n_states, 65535), std::max<int64_t>(1, 4096 / per_state));
+  const dim3 grid((unsigned)n_chunks, (unsigned)n_tiles, (unsigned)gz);
+#define RYD_OVERLAP_LAUNCH_T(FORM, TRACE, TILE)                                                                          \
+  hipLaunchKernelGGL((k_overlap_many<FORM, TRACE, TILE>), grid, dim3(256), 0, st, (const cplx*)states_dev,               \
+                     (long long)n_states, (long long)stride, (long long)dim, (long long)len, (const cplx*)targets_dev,   \
+                     (int)n_targets, (double*)out_dev, norm_dev)
+#define RYD_OVERLAP_LAUNCH(FORM, TRACE)                  \
+  do {                                                   \
+    if (tile == 1)                                       \
+      RYD_OVERLAP_LAUNCH_T(FORM, TRACE, 1);              \
+    else                                                 \
+      RYD_OVERLAP_LAUNCH_T(FORM, TRACE, kOverlapTile);   \
+  } while (0)
+  if (!density)
+    RYD_OVERLAP_LAUNCH(0, 0);
+  else if (target_form)
+    RYD_OVERLAP_LAUNCH(1, 1);
+  else
+    RYD_OVERLAP_LAUNCH(0, 1);
+#undef RYD_OVERLAP_LAUNCH
+#undef RYD_OVERLAP_LAUNCH_T
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(RYD_ERR_HIP, "k_overlap_many: %s", hipGetErrorString(e));
+  return RYD_OK;
+}
+
 extern "C" int ryd_accumulate(const void* x_dev, double weight, int64_t count, void* acc_dev,
                               int32_t device, void* stream) {
   if (!x_dev || !acc_dev || count <= 0) return fail(RYD_ERR_INVALID, "null argument or empty array");

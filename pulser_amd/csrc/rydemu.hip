@@ -72,6 +72,7 @@ SPLITR_INSTANCES_14(SPLITR_EXTERN)
 #include "k_observe.hpp"
 #include "k_gen_observe.hpp"
 #include "k_expect.hpp"
+#include "k_overlap.hpp"
 #include "k_general.hpp"
 #include "host_handle.hpp"
 #include "host_apply.hpp"

@@ -165,6 +165,61 @@ def expect_sparse(states: Any, operator: Any, *, density: bool = False) -> Any:
     return out
 
 
+def overlap_many(states: Any, targets: Any, *, density: bool = False, outer: bool = False) -> tuple[Any, Any]:
+    """``z[s, f] = <a_f|x_s>`` and ``norm[s] = <x_s|x_s>`` for kets ``states`` complex128[S, D]; with ``density=True``,
+    ``states`` complex128[S, D, D], ``z[s, f] = Tr(A_f^dag rho_s)`` for matrix targets or, with ``outer=True``,
+    ``<phi_f|rho_s|phi_f>`` for ket targets (``|phi><phi|`` is never formed), and ``norm[s] = Re Tr rho_s`` - for every
+    state and target in one launch (``ryd_overlap_many``): ``QutipState.overlap`` of qutip_state.py:86-110 over the
+    states of a run, with the number each state is normalised by.  ``states`` is a CUDA tensor whose inner dimensions
+    are contiguous; dim 0 may be strided (``dev[:, b]`` of a ``[T, B, D]`` snapshot tensor).  ``targets`` is a CUDA
+    tensor or a host array, ``[F, D]`` (kets, or ``outer``) or ``[F, D * D]`` / ``[F, D, D]`` (matrix targets); F = 0
+    gives the norms alone.  Returns CUDA tensors ``z`` complex128[S, F] and ``norm`` float64[S]."""
+    torch = _torch()
+    if not (hasattr(states, "is_cuda") and states.is_cuda):
+        raise ValueError("states must be a CUDA tensor")
+    if states.dtype != torch.complex128:
+        raise TypeError("complex128 tensor expected")
+    if outer and not density:
+        raise ValueError("outer=True (ket targets on density matrices) needs density=True")
+    if states.dim() != (3 if density else 2) or (density and states.shape[1] != states.shape[2]):
+        raise ValueError(f"shape {tuple(states.shape)} does not match {'[S, D, D]' if density else '[S, D]'}")
+    n_states, dim = int(states.shape[0]), int(states.shape[-1])
+    inner = (dim, 1) if density else (1,)
+    elems = dim ** len(inner)
+    if dim < 1 or (n_states > 0 and tuple(states.stride()[1:]) != inner) or (n_states > 1 and states.stride(0) < elems):
+        raise ValueError("the inner dimensions of states must be contiguous (dim 0 may be strided)")
+    tlen = dim if outer else elems
+    if isinstance(targets, torch.Tensor):
+        if targets.dtype != torch.complex128:
+            raise TypeError(f"complex128 targets expected, got {targets.dtype}")
+        if targets.device != states.device and targets.is_cuda:
+            raise ValueError(f"targets on {targets.device}, states on {states.device}")
+        tg = targets
+    else:
+        host = np.asarray(targets)
+        if host.dtype.kind not in "biufc":
+            raise TypeError(f"numeric targets expected, got {host.dtype}")
+        tg = torch.from_numpy(np.ascontiguousarray(host, dtype=np.complex128))
+    shapes = [(tlen,)] + ([(dim, dim)] if density and not outer else [])
+    if tg.dim() < 2 or tuple(int(v) for v in tg.shape[1:]) not in shapes:
+        raise ValueError(f"targets of shape {tuple(tg.shape)} do not match "
+                         + " or ".join(f"[F, {', '.join(map(str, s))}]" for s in shapes))
+    n_targets = int(tg.shape[0])
+    if n_targets > 4 * 65535:  # (tiles of 4 targets along one grid dimension)
+        raise ValueError(f"{n_targets} targets: at most {4 * 65535}")
+    tg = tg.reshape(n_targets, tlen).contiguous().to(states.device)
+    z = torch.empty((n_states, n_targets), dtype=torch.complex128, device=states.device)
+    norm = torch.empty(n_states, dtype=torch.float64, device=states.device)
+    if n_states == 0:
+        return z, norm
+    stride = int(states.stride(0)) if n_states > 1 else elems
+    _lib.check(_lib.load().ryd_overlap_many(
+        states.data_ptr(), n_states, stride, dim, int(bool(density)), tg.data_ptr() if n_targets else None, n_targets,
+        int(bool(outer)), z.data_ptr() if n_targets else None, norm.data_ptr(), int(states.device.index or 0),
+        torch.cuda.current_stream(states.device).cuda_stream))
+    return z, norm
+
+
 class Engine:
     """One ``ryd_handle``: a batch of B states of N atoms on one device.
 
