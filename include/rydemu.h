@@ -576,6 +576,22 @@ int ryd_overlap_many(const void* states_dev, int64_t n_states, int64_t stride, i
                      const void* targets_dev, int32_t n_targets, int32_t target_form,
                      void* out_dev, double* norm_dev, int32_t device, void* stream);
 
+/* Replaces: the diagonal of density_matrix_aggregator's sum of |psi><psi| over quantum-jump trajectories
+ * (pulser_simulation/aggregators.py:20-37) at every evaluation time - all that the sampling of the averaged state reads
+ * (QutipResult._weights, pulser_simulation/qutip_result.py:101-118) - without the dim x dim matrices:
+ *   diag[i][x] += sum_b |psi(i, b)[x]|^2     i < n_times, b < n_batch, x < dim;  one launch.
+ * state (i, b) starts at states_dev + i*stride_t + b*stride_b (complex128 elements, 64-bit offsets; both strides >= dim,
+ * else RYD_ERR_INVALID) and is contiguous over dim.  No handle and any dim >= 1, not only powers of two.
+ * diag_dev float64[n_times][dim], contiguous, is ACCUMULATED into: zero it once, then call once per chunk of
+ * trajectories.  No atomics: every entry is summed by one lane in the order b = 0 .. n_batch - 1 onto the value found,
+ * whatever the launch geometry, so two calls on the same input give bitwise equal output.
+ * n_times = 0 returns RYD_OK and launches nothing.  Null pointers, n_times < 0, n_batch < 1, dim < 1, a stride below dim:
+ * RYD_ERR_INVALID.  No host synchronisation. */
+int ryd_ensemble_diag(const void* states_dev, int32_t n_times, int32_t n_batch,
+                      int64_t stride_t, int64_t stride_b, int64_t dim,
+                      double* diag_dev /* float64[n_times][dim] */,
+                      int32_t device, void* stream);
+
 int ryd_get_stats(const ryd_handle* h, ryd_stats* out);
 int ryd_reset_stats(ryd_handle* h);
 

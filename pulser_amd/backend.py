@@ -29,7 +29,7 @@ from typing import Any, Callable, Mapping, Sequence
 import numpy as np
 
 from .noise_model import NoiseModel, has_stochastic_noise
-from .results import DeviceState, LazyState, QState, multinomial
+from .results import DeviceState, EnsembleState, LazyState, QState, multinomial
 from .simulation import QutipEmulator, Solver
 
 __all__ = [
@@ -1660,6 +1660,21 @@ def _overlap_many_route(states: Sequence[Any], fires: Sequence[bool],
     return store, b, positions, len(tail) == 2
 
 
+def _mc_ensemble_route(sim: QutipEmulator, config: "QutipConfig") -> bool:
+    """Whether a run with ``QutipBackendV2.mc_ensemble = True`` takes ``QutipEmulator.run(mc_ensemble=True)``: the
+    deterministic-noise quantum-jump run on the tuned two-level jump kernels, no callbacks, and nothing but observables
+    that are linear in the averaged state's diagonal or served by the trajectory means (``BitStrings``, ``Occupation``,
+    ``CorrelationMatrix``, ``Energy``, ``EnergySecondMoment``, ``EnergyVariance`` themselves, not subclasses).  Anything
+    else (``StateResult``, ``Fidelity``, ``Expectation``, a callback) reads the density matrix: today's route."""
+    if has_stochastic_noise(sim.noise_model) or config.callbacks:
+        return False
+    allowed = (BitStrings, Occupation, CorrelationMatrix, Energy, EnergySecondMoment, EnergyVariance)
+    if not all(type(o) in allowed for o in config.observables):
+        return False
+    problem = sim._current_problem
+    return sim._solver_mode(problem) == "mcsolve" and sim._mc_fast_ok(problem)
+
+
 # ------------------------------------------------------------------- backend
 class QutipBackendV2:
     """qutip_backend.py:121-325 on the MI355X engine.  ``sequence`` is a
@@ -1688,6 +1703,11 @@ class QutipBackendV2:
     # operator) from max(observe_many_min_times, this floor) evaluation times on.  (The value is carried over from the
     # routes above and was not tuned for this one; profiles/overlap_many.md has timings at 128 and above, none below.)
     _OVERLAP_MANY_FLOOR = 128
+    # True: a deterministic-noise quantum-jump run on the two-level jump kernels whose observables need nothing but the
+    # diagonal and the trajectory means (_mc_ensemble_route) never forms the averaged density matrices
+    # (QutipEmulator.run(mc_ensemble=True)): d^N numbers per trajectory, no 16-GiB cap on the evaluation times.  Values
+    # agree with the default route's within rounding, not bit for bit; every other run is left exactly as it is.
+    mc_ensemble: bool = False
 
     def __init__(self, sequence: Any, *, config: QutipConfig | None = None,
                  mimic_qpu: bool = False) -> None:
@@ -1739,7 +1759,7 @@ class QutipBackendV2:
 
     def run(self) -> Results:
         return self._run_raw(self._sim_obj, self._config, dict(self._options),
-                             observe_many_min_times=self.observe_many_min_times)
+                             observe_many_min_times=self.observe_many_min_times, mc_ensemble=self.mc_ensemble)
 
     @staticmethod
     def run_from_sequence_samples(sequence_samples: Any, register: Any = None, device: Any = None,
@@ -1754,9 +1774,10 @@ class QutipBackendV2:
 
     @staticmethod
     def _run_raw(sim: QutipEmulator, config: QutipConfig, options: dict[str, Any], *,
-                 observe_many_min_times: Any = "class") -> Results:
+                 observe_many_min_times: Any = "class", mc_ensemble: bool = False) -> Results:
         """``observe_many_min_times``: the threshold of the one-call observable path for this run (``run`` passes the
-        instance's, so a subclass or an instance may set its own); by default the class attribute."""
+        instance's, so a subclass or an instance may set its own); by default the class attribute.  ``mc_ensemble``:
+        the instance's ``QutipBackendV2.mc_ensemble``; it takes effect where ``_mc_ensemble_route`` allows."""
         from .engine import Engine, GeneralEngine
         from .general import lower_general
         from .terms import SUPPORTED_BASES
@@ -1855,6 +1876,10 @@ class QutipBackendV2:
             if firing >= max(int(min_times), QutipBackendV2._OVERLAP_MANY_FLOOR):
                 options = {**options, "general_device_snapshots": True}
         overlap_cache: dict[str, Any] = {}  # like many_cache, for overlapped_many
+        if mc_ensemble and _mc_ensemble_route(sim, config):
+            # the energy moments of the trajectories are those of the H(t) every HamiltonianOperator below wraps (the
+            # engine is built before the solve here: a two-level run without stochastic noise draws nothing for it)
+            options = {**options, "mc_ensemble": True, "mc_ensemble_observer": noiseless_engine()}
 
         def overlapped_many(rs: Sequence[Any]) -> dict[int, tuple[dict[Any, np.ndarray], int, int]]:
             """position in ``rs`` -> (finished values [row, column] by observable, its row, its column), {} on the
@@ -1973,9 +1998,14 @@ class QutipBackendV2:
                             if o.uuid in values:
                                 v = values[o.uuid][row, col]
                                 state.seed(o, float(v) if isinstance(o, Fidelity) else complex(v))
+                elif isinstance(r.state, EnsembleState):  # served from its diagonal and its trajectory means
+                    state = RydState(r.state, eigenstates=eigenstates)
                 else:
                     state = RydState(r.state.unit(), eigenstates=eigenstates)
                 ham = HamiltonianOperator(noiseless_engine(), t * T / 1000, eigenstates, energy_expected=wants_energy)
+                if isinstance(r.state, EnsembleState):
+                    e = r.state
+                    ham.seed(state, e.norm2, e.occupation, e.correlation, e.energy, e.energy2)
                 if served is not None:
                     by_digit, row, b = served
                     for k, (d, got) in enumerate(by_digit.items()):

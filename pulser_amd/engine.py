@@ -104,6 +104,39 @@ def outer_accumulate(psi: Any, acc: Any, weights: Any = None) -> None:
         torch.cuda.current_stream(psi.device).cuda_stream))
 
 
+def ensemble_diag(states: Any, diag: Any) -> None:
+    """``diag[i, x] += sum_b |states[i, b, x]|^2`` on the device, without a solver handle and for any state dimension
+    (``ryd_ensemble_diag``): the diagonal of the trajectory sum of pulser_simulation/aggregators.py:20-37 at every
+    evaluation time, all that sampling the averaged state reads - the ``[D, D]`` matrices are never formed.  ``states``
+    is a complex128 CUDA tensor ``[T, B >= 1, D]`` or a view of one whose last axis is contiguous (the strides of the
+    first two axes are passed on); ``diag`` is a contiguous float64 ``[T, D]`` on the same device and is accumulated
+    into: zero it once, call once per chunk of trajectories.  No atomics: repeated calls give bitwise equal sums."""
+    torch = _torch()
+    if not (isinstance(states, torch.Tensor) and isinstance(diag, torch.Tensor)
+            and states.is_cuda and diag.is_cuda and states.device == diag.device):
+        raise ValueError("states and diag must be CUDA tensors on the same device")
+    if states.dtype != torch.complex128 or diag.dtype != torch.float64:
+        raise TypeError("a complex128 states tensor and a float64 diag tensor expected")
+    if states.dim() != 3 or int(states.shape[1]) < 1 or int(states.shape[2]) < 1 \
+            or tuple(diag.shape) != (states.shape[0], states.shape[2]):
+        raise ValueError(f"shapes {tuple(states.shape)} / {tuple(diag.shape)} do not match [T, B >= 1, D] / [T, D]")
+    if not diag.is_contiguous():
+        raise ValueError("a contiguous diag tensor expected")
+    n_t, n_b, dim = (int(v) for v in states.shape)
+    if n_t == 0:
+        return
+    if states.stride(2) != 1 and dim > 1:
+        raise ValueError("the last axis of states must be contiguous (the first two may be strided)")
+    # (the stride of an axis of length 1 is arbitrary in torch and never used: any valid value will do)
+    stride_b = int(states.stride(1)) if n_b > 1 else dim
+    stride_t = int(states.stride(0)) if n_t > 1 else max(n_b * stride_b, dim)
+    if stride_b < dim or stride_t < dim:
+        raise ValueError(f"strides {stride_t} / {stride_b} of the first two axes are smaller than a state ({dim})")
+    _lib.check(_lib.load().ryd_ensemble_diag(
+        states.data_ptr(), n_t, n_b, stride_t, stride_b, dim, diag.data_ptr(), int(states.device.index or 0),
+        torch.cuda.current_stream(states.device).cuda_stream))
+
+
 def accumulate(x: Any, acc: Any, weight: float = 1.0) -> None:
     """``acc += weight * x`` elementwise on the device (``ryd_accumulate``): the running sum of
     trajectory density matrices of aggregators.py:29-35."""

@@ -158,6 +158,76 @@ class DeviceState:
         return f"DeviceState(shape={self.shape}, {where})"
 
 
+class EnsembleState(DeviceState):
+    """The trajectory-averaged state ``mean_b |psi_b><psi_b|`` of a quantum-jump run (``run(mc_ensemble=True)``) at
+    one evaluation time, held as what is linear in it and was reduced from the kets on the device: the diagonal
+    (``ryd_ensemble_diag``) and the trajectory means of the built-in observables (``ryd_observe_many``).  The
+    ``[D, D]`` matrix never exists, on the device or here.
+
+    Like :class:`DeviceState` it answers ``shape``, ``isket``, ``diag()`` and ``tr()`` - all that sampling reads
+    (qutip_result.py:101-118) - so ``get_samples``, ``sampling_dist``, ``sample_state`` and the SPAM flips work
+    unchanged.  Whatever needs an off-diagonal entry raises ``NotImplementedError``.
+
+    ``occupation`` [N] and ``correlation`` [N, N] count local state 0 (the first eigenstate), as ``Engine.observe``
+    does; ``energy`` / ``energy2`` are the moments of the noiseless H(t); ``norm2`` is the mean squared norm of the
+    kets (~ 1).  None of them is divided by ``norm2``.  ``occupation_stderr`` [N] is the sample standard deviation of
+    the per-trajectory occupations over sqrt(n_trajectories): the Monte-Carlo error of ``occupation``."""
+
+    _REFUSAL = ("the trajectory-averaged density matrix was never formed (mc_ensemble=True keeps its diagonal and "
+                "the means of the built-in observables): run with mc_ensemble=False for {}")
+
+    def __init__(self, diag_sum: np.ndarray, n_trajectories: int, *, occupation: np.ndarray,
+                 correlation: np.ndarray, energy: float, energy2: float, norm2: float,
+                 occupation_stderr: np.ndarray) -> None:
+        d = np.asarray(diag_sum, dtype=np.float64).reshape(-1)
+        if n_trajectories < 1:
+            raise ValueError(f"n_trajectories must be at least 1, got {n_trajectories}")
+        self._tensor = None
+        self._ket = None
+        self.n_trajectories = int(n_trajectories)
+        self._diag = (d / self.n_trajectories).astype(complex)
+        self.occupation = np.asarray(occupation, dtype=np.float64)
+        self.correlation = np.asarray(correlation, dtype=np.float64)
+        self.energy = float(energy)
+        self.energy2 = float(energy2)
+        self.norm2 = float(norm2)
+        self.occupation_stderr = np.asarray(occupation_stderr, dtype=np.float64)
+
+    @property
+    def shape(self) -> tuple[int, int]:
+        return (int(self._diag.size), int(self._diag.size))
+
+    def diag(self) -> np.ndarray:
+        return self._diag
+
+    def _refuse(self, what: str) -> Any:
+        raise NotImplementedError(self._REFUSAL.format(what))
+
+    def full(self) -> np.ndarray:
+        return self._refuse("full()")
+
+    def copy(self) -> np.ndarray:
+        return self._refuse("copy()")
+
+    def __array__(self, dtype: Any = None, copy: Any = None) -> np.ndarray:
+        return self._refuse("np.asarray")
+
+    def dag(self) -> "QState":
+        return self._refuse("dag()")
+
+    def norm(self) -> float:
+        return self._refuse("norm()")
+
+    def unit(self) -> "QState":
+        return self._refuse("unit()")
+
+    def overlap(self, other: Any) -> complex:
+        return self._refuse("overlap()")
+
+    def __repr__(self) -> str:
+        return f"EnsembleState(shape={self.shape}, n_trajectories={self.n_trajectories})"
+
+
 class SnapshotStore:
     """The evaluation-time snapshots of one solve, ``[n_times - 1, B, dim...]`` on the GPU, and their host copies.
 
@@ -776,6 +846,16 @@ class SimulationResults(collections.abc.Sequence):
                 herm = bool(np.all(dm.data <= 1e-8 + 1e-5 * np.asarray(ref[dm.row, dm.col]).reshape(-1))) if dm.nnz else True
             else:
                 herm = bool(np.allclose(m, m.conj().T))
+            if any(isinstance(st, EnsembleState) for st in states):
+                # a trajectory ensemble kept as its diagonal: Tr(m rho) of an exactly diagonal m needs nothing else
+                if not is_diag:
+                    raise NotImplementedError(EnsembleState._REFUSAL.format("the expectation value of an operator "
+                                                                            "that is not diagonal"))
+                d = np.asarray(m.diagonal())
+                vals = [np.sum(d * (st.diag() if not st.isket else np.abs(np.asarray(st).reshape(-1)) ** 2))
+                        for st in states]
+                out.append(np.array([v.real if herm else v for v in vals]))
+                continue
             if is_diag and not self._use_pseudo_dens:
                 d = np.asarray(m.diagonal())
                 fast = self._expect_diagonal_on_device(states, d.real.copy() if herm else d.astype(complex))

@@ -30,7 +30,7 @@ import numpy as np
 from .hamiltonian_data import HamiltonianData, SequenceInputs
 from .noise_model import (LEGACY_DEFAULTS, NoiseModel, _NOISE_TYPE_PARAMS,
                           check_eff_noise, has_stochastic_noise)
-from .results import (DeviceState, CoherentResults, LazyState, NoisyResults, QState, SampledResult,
+from .results import (DeviceState, CoherentResults, EnsembleState, LazyState, NoisyResults, QState, SampledResult,
                       SimulationResults, SnapshotStore, StateResult)
 from .terms import sampling_times
 
@@ -864,6 +864,8 @@ class QutipEmulator:
                 mode = "mesolve"
             if mode == "mcsolve":
                 if mc_ntraj is not None:
+                    if options.get("mc_ensemble"):
+                        return [self._solve_mc_ensemble(problems[0], mc_ntraj, options)]
                     return [self._solve_mc_average(problems[0], mc_ntraj, options)]
             elif not self._fast_path_ok(problems[0]):
                 return self._solve_general(problems, mode, options)
@@ -1030,6 +1032,98 @@ class QutipEmulator:
         ]
         return CoherentResults(results, n, self.basis_name, times, self._meas_basis, meas_errors)
 
+    def _solve_mc_ensemble(self, problem: dict[str, Any], ntraj: int,
+                           options: dict[str, Any]) -> CoherentResults:
+        """The deterministic quantum-jump run of :meth:`_solve_mc_average` (``run(mc_ensemble=True)``) without the
+        averaged density matrices: the same chunks, seeds and kernels integrate the same trajectories, and what is
+        linear in ``mean_b |psi_b><psi_b|`` is reduced from the kets - the diagonal by ``ensemble_diag``, the
+        occupations, correlations and energy moments by ``observe_many`` of a noiseless batch-1 engine (the option
+        ``mc_ensemble_observer`` hands one in; it is then left open) - and summed over the trajectories on the host.
+        Memory is d^N per trajectory, never d^2N; the results hold :class:`EnsembleState` objects."""
+        from .engine import Engine, ensemble_diag
+        from .terms import lower
+
+        times = self._eval_times_array
+        n = self._hamiltonian_data.n_qudits
+        D = 2 ** n
+        init = np.asarray(self._initial_state)
+        if init.ndim == 2 and init.shape[0] == init.shape[1] and init.shape[0] > 1:
+            raise NotImplementedError(
+                "Quantum-jump trajectories need a ket as initial state; use "
+                "solver=Solver.MESOLVER with a density matrix.")
+        chunk = int(max(1, min(ntraj, 1024, (2 << 30) // max(1, D * 16 * len(times)))))
+        # per evaluation time: one row of the diagonals and the kets of one chunk (the solver's work copies are kets too)
+        self._check_snapshot_budget(len(times) - 1, D * 8 + chunk * D * 16,
+                                    "evaluation time (the ensemble diagonal and one chunk of kets)")
+        observer = options.get("mc_ensemble_observer")
+        own_observer = observer is None
+        if own_observer:
+            noiseless = dict(problem)
+            noiseless["collapse_ops"] = []
+            observer = Engine.from_problems([noiseless], mode="sesolve")
+        t_us = np.asarray(times, dtype=np.float64)
+        sums: dict[str, np.ndarray] = {}
+        occ_sq = np.zeros((len(times), n))
+
+        def add(rows: dict[str, np.ndarray], at: slice, weight: int = 1) -> None:
+            # rows: [T', B, ...] per trajectory, not normalised -> the sums over the trajectory axis
+            for k, v in rows.items():
+                if k not in sums:
+                    sums[k] = np.zeros((len(times),) + tuple(v.shape[2:]))
+                sums[k][at] += weight * v.sum(axis=1)
+            occ_sq[at] += weight * (rows["occupation"] ** 2).sum(axis=1)
+
+        try:
+            torch = observer.torch
+            diag = torch.zeros((len(times), D), dtype=torch.float64, device=observer.device)
+            first = observer.new_state(init.reshape(1, -1))[None]  # [1, 1, D]: every trajectory starts here
+            ensemble_diag(first, diag[:1])
+            diag[0] *= ntraj
+            add(observer.observe_many(first, t_us[:1], energy=True), slice(0, 1), ntraj)
+            del first
+            done = 0
+            jumps = []
+            while done < ntraj:
+                b = min(chunk, ntraj - done)
+                tables = lower([problem] * b)
+                with Engine(tables, mode="mcsolve") as eng:
+                    state = eng.new_state(init.reshape(1, -1))
+                    snaps = eng.mc_solve(state, times, self._mc_seeds(b, options), store=True,
+                                         **self._engine_kwargs(options))
+                    ensemble_diag(snaps, diag[1:])
+                    add(observer.observe_many(snaps, t_us[1:], energy=True), slice(1, None))
+                    jumps.append(eng.mc_jumps())
+                    self.last_engine_stats = eng.stats()
+                    del state, snaps
+                done += b
+            host = diag.cpu().numpy()
+            del diag
+        finally:
+            if own_observer:
+                observer.close()
+        self.last_mc_jumps = np.concatenate(jumps)
+        mean_occ = sums["occupation"] / ntraj
+        with np.errstate(invalid="ignore", divide="ignore"):  # (one trajectory has no sample deviation: nan)
+            var = np.maximum(occ_sq - ntraj * mean_occ ** 2, 0.0) / (ntraj - 1) if ntraj > 1 else np.full_like(occ_sq, np.nan)
+            stderr = np.sqrt(var / ntraj)
+        if ntraj > 1:
+            stderr[0] = 0.0  # every trajectory starts in the same ket (not left to the rounding of sum x^2 - n mean^2)
+        meas_errors = (
+            {"epsilon": self.noise_model.p_false_pos, "epsilon_prime": self.noise_model.p_false_neg}
+            if "SPAM" in self.noise_model.noise_types else None
+        )
+        qids = tuple(self.samples_obj.qubit_ids)
+        results = [
+            StateResult(qids, self._meas_basis,
+                        EnsembleState(host[i], ntraj, occupation=mean_occ[i], correlation=sums["correlation"][i] / ntraj,
+                                      energy=sums["energy"][i] / ntraj, energy2=sums["energy2"][i] / ntraj,
+                                      norm2=sums["norm2"][i] / ntraj, occupation_stderr=stderr[i]),
+                        self._meas_basis in self.basis_name,
+                        evaluation_time=float(t / (self._tot_duration * 1e-3)))
+            for i, t in enumerate(times)
+        ]
+        return CoherentResults(results, n, self.basis_name, times, self._meas_basis, meas_errors)
+
     def _solve_general(self, problems: list[dict[str, Any]], mode: str,
                        options: dict[str, Any]) -> list[CoherentResults]:
         from .engine import GeneralEngine
@@ -1188,7 +1282,19 @@ class QutipEmulator:
 
         ``general_device_snapshots=True``: the kets of a multi-level / XY run without collapse operators stay on the
         GPU (one ``SnapshotStore`` per trajectory) and ``results.states`` holds ``LazyState`` objects that cross PCIe
-        when they are read, as the states of a 2-level run do; by default they are host ``QState`` objects."""
+        when they are read, as the states of a 2-level run do; by default they are host ``QState`` objects.
+
+        ``mc_ensemble=True``: the deterministic-noise quantum-jump run on the tuned 2-level jump kernels
+        (``Solver.MCSOLVER`` / ``n_trajectories`` on one Hamiltonian) keeps d^N numbers per trajectory to the end: the
+        trajectory-averaged density matrices are not formed, so the evaluation-time list is no longer capped by
+        16 GiB of ``[D, D]`` accumulators (3 times at 14 atoms).  The same trajectories run on the same kernels with
+        the same ``seeds=``; the results hold ``EnsembleState`` objects - the diagonal of the averaged state
+        (sampling, ``sampling_dist``, the SPAM flips and ``expect`` of diagonal operators work unchanged) and the
+        trajectory means ``occupation``, ``correlation``, ``energy``, ``energy2``, ``norm2`` with
+        ``occupation_stderr``, equal to the values of the averaged matrix within rounding.  ``full()``, ``overlap``
+        and ``expect`` of other operators raise ``NotImplementedError``.  Every other run ignores the option.
+        ``mc_ensemble_observer``: a noiseless batch-1 sesolve ``Engine`` whose H(t) the energy moments use (left
+        open); by default one is built from the run's problem without its collapse operators."""
         warnings.warn(
             "QutipEmulator is deprecated as of pulser 1.9. Please use QutipBackendV2 instead.",
             DeprecationWarning,
