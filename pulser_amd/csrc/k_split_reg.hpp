@@ -59,13 +59,35 @@
 #define SPLITR_WMODE 1
 #endif
 //   SPLITR_EMODE 1: the per-lane E0 pieces et / eg of both layouts in LDS (read once per stage) instead of 8 registers
-//   SPLITR_KWARM 1: the next stage's coefficient record is touched (one scalar load per 64-B line) half a stage ahead
+//   SPLITR_KWARM: the next stage's coefficient record (written by k_split_coefs, never read by this CU: a cold miss) is
+//                touched half a stage ahead (profiles/stage_waits.md)
+//                1: one scalar load per 64-B line right behind the first barrier of the pass, folded on the spot: every
+//                   wave of the workgroup waits out the miss there, a few cycles after they all left the same barrier;
+//                2 (default): the same loads behind the phase factors of the last group, folded only in front of the
+//                   pass's first barrier: ~460 vector instructions without an LDS read or a scalar load lie in between
+//                   (scalar loads return out of order, so ANY wait on the LDS / scalar counter while a touch is in flight
+//                   is a full wait - the placement is the point; between the group loop and pre(C0), fenced on both sides,
+//                   they cost more than half of the gain);
+//                3: ONE vector load per wave at the same place, lane k on line k: warms the L2 only, its value is
+//                   consumed a stage later (the vector counter: no wait inside the stage)
 //   SPLITR_PREF  1: the detuning integrals and the E0 weight of the NEXT stage are loaded at the end of a stage
 #ifndef SPLITR_EMODE
 #define SPLITR_EMODE 0
 #endif
 #ifndef SPLITR_KWARM
-#define SPLITR_KWARM 1
+#define SPLITR_KWARM 2
+#endif
+//   SPLITR_GAHEAD (SPLITR_TMODE 1 with two T bits, SPLITR_GMODE 0; profiles/stage_waits.md): the LDS reads of the phase
+//                factors are issued long before their values are needed instead of 4 - 8 fp64 instructions ahead:
+//                0: G(r) is read where phase_group uses it, the table entry of an expmi inside it;
+//                1 (default): the seven table reads of the stage's expmi are issued as soon as their indices exist,
+//                   in front of the series of all seven; G's own factor comes first, so that the four G values of the first
+//                   group are read behind it and arrive under the six other series; the four G values of group g - 1 are
+//                   read at the start of group g's work into registers of their own (16 on top of the 229);
+//                2: the G values of group g - 1 are read behind group g's phase factors (no second set of G registers)
+//                Complex drives and the row kernels keep the old order (256 vector registers without it).
+#ifndef SPLITR_GAHEAD
+#define SPLITR_GAHEAD 1
 #endif
 #ifndef SPLITR_PREF
 #define SPLITR_PREF 0
@@ -278,11 +300,14 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
   __syncthreads();
   typedef const __attribute__((address_space(4))) double* cptr_t;
   // exp(-i phi) = (cos, -sin): table of exp(2 pi i k / SPLITR_TRIG), series on |rr| <= pi / SPLITR_TRIG
-  auto expmi = [&](double phi) -> cplx {
+  // (two halves, so that a stage can issue the table reads of all its phases before the first series: SPLITR_GAHEAD)
+  auto expmi_arg = [&](double phi, double& rr) -> cplx {  // the table entry; rr = the reduced argument
     const double kk = rint(phi * (SPLITR_TRIG / 6.283185307179586));
-    double rr = fma(-kk, 6.283185307179586 / SPLITR_TRIG, phi);
+    rr = fma(-kk, 6.283185307179586 / SPLITR_TRIG, phi);
     rr = fma(-kk, 2.4492935982947064e-16 / SPLITR_TRIG, rr);  // 2 pi - double(2 pi)
-    const cplx tb = trig[((int)kk) & (SPLITR_TRIG - 1)];
+    return trig[((int)kk) & (SPLITR_TRIG - 1)];
+  };
+  auto expmi_fin = [&](double rr, cplx tb) -> cplx {
     const double r2 = rr * rr;
     double cr, sr;
     if (SPLITR_TRIG >= 512) {  // |rr| <= pi / 512: the next terms are below 1e-19
@@ -293,6 +318,11 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
       sr = rr * fma(r2, fma(r2, fma(r2, -1.984126984126984e-04, 8.333333333333333e-03), -1.6666666666666666e-01), 1.0);
     }
     return make_double2(fma(tb.x, cr, -tb.y * sr), -fma(tb.y, cr, tb.x * sr));
+  };
+  auto expmi = [&](double phi) -> cplx {
+    double rr;
+    const cplx tb = expmi_arg(phi, rr);
+    return expmi_fin(rr, tb);
   };
   auto cm = [](cplx a, cplx c) -> cplx { return make_double2(fma(a.x, c.x, -a.y * c.y), fma(a.x, c.y, a.y * c.x)); };
   // private slice of buffer 0: the slots a wave's own pass stores go to (slot = l + 64 (w + NG q), q < CH)
@@ -357,6 +387,8 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
   };
   if (SPLITR_PREF) load_next(0, false);
   unsigned warm = 0;
+  unsigned warm_v = 0, warm_va = 0;  // SPLITR_KWARM 3: the value in flight and the fold of the earlier ones (per lane)
+  const unsigned long long stage_bytes = (unsigned long long)stage_stride * sizeof(double);
   // One stage.  PLAIN_CLOSE: the closing stage of a run without a closing kick - D only (its rotation angles are zero):
   // the phase factors and nothing else, the layout stays (an instantiation of the same body after the loop: the loop's
   // back edge sees one register assignment)
@@ -429,18 +461,54 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
 
     // ---- the lane's phase factors ----
     cplx Bf, F[NR], Gl;
+    // SPLITR_GAHEAD: the shapes and builds that read their phase tables ahead; Gq = the G values of the group whose
+    // phase factors come next (register r = g | (rho << NW) in Gq[rho])
+    // (not ROWS, not CPLX: the 16 registers do not fit there - the row kernel spills 22 vector registers instead of 12)
+    constexpr bool kGAhead = SPLITR_GAHEAD != 0 && !SPLITR_GMODE && SPLITR_TMODE == 1 && NTB == 2 && !CPLX && !ROWS && !PLAIN_CLOSE && !(SPLITR_KO & 8);
+    cplx Gq[GR];
+    auto g_fetch = [&](auto Gc) {
+      constexpr int g = decltype(Gc)::value;
+      const cplx* __restrict__ gq = gtab + w * NA;
+      splitr_for<0, GR>([&](auto Ic) {
+        constexpr int rho = GR - 1 - decltype(Ic)::value;  // (the order phase_group uses them in)
+        Gq[rho] = gq[g | (rho << NW)];
+      });
+    };
     if (!(SPLITR_KO & 8)) {
       double dthr = 0.0;
 #pragma unroll
       for (int j = 0; j < 6; ++j) dthr += ((tq >> j) & 1u) ? 0.0 : Dl[j];
 #pragma unroll
       for (int j = 0; j < NW; ++j) dthr += ((tq >> (6 + j)) & 1u) ? 0.0 : Dw[j];
-      Bf = expmi(fma(wE, et_s, -dthr));
       double sc = cprod;
       if (DECAY)  // H_eff: the real factor exp(wE (dec_a + dec_b popc(index))): lane part here, register part in F
         sc *= exp(wE * (A.dec_a + A.dec_b * (double)(__popc(tq) + NR)));
-      Bf = make_double2(Bf.x * sc, Bf.y * sc);
       const double dF = DECAY ? exp(-wE * A.dec_b) : 1.0;  // an excited register atom: one set bit fewer
+      if constexpr (kGAhead) {
+        // the same seven expmi on the same arguments; only the order of issue differs: table reads, G's series, the G
+        // table and the first group's reads of it, then the other six series (which cover those reads)
+        double rB, rF[NR], rG;
+        const cplx tG = expmi_arg(wE * eg_s, rG);
+        const cplx tB = expmi_arg(fma(wE, et_s, -dthr), rB);
+        cplx tF[NR];
+#pragma unroll
+        for (int j = 0; j < NR; ++j) tF[j] = expmi_arg(fma(wE, odd ? ev[1][j] : ev[0][j], -Dr[j]), rF[j]);
+        __builtin_amdgcn_sched_barrier(0);
+        Gl = expmi_fin(rG, tG);
+        gtab[w * NA + (l & (NA - 1))] = Gl;
+        __builtin_amdgcn_wave_barrier();
+        g_fetch(splitr_c<NG - 1>{});
+        __builtin_amdgcn_sched_barrier(0);
+        Bf = expmi_fin(rB, tB);
+        Bf = make_double2(Bf.x * sc, Bf.y * sc);
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+          F[j] = expmi_fin(rF[j], tF[j]);
+          if (DECAY) F[j] = make_double2(F[j].x * dF, F[j].y * dF);
+        }
+      } else {
+      Bf = expmi(fma(wE, et_s, -dthr));
+      Bf = make_double2(Bf.x * sc, Bf.y * sc);
 #pragma unroll
       for (int j = 0; j < NR; ++j) {
         F[j] = expmi(fma(wE, odd ? ev[1][j] : ev[0][j], -Dr[j]));
@@ -450,6 +518,7 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
       if (!SPLITR_GMODE) {
         gtab[w * NA + (l & (NA - 1))] = Gl;
         __builtin_amdgcn_wave_barrier();
+      }
       }
     }
     if (kLate && !PLAIN_CLOSE) {
@@ -476,6 +545,14 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
     auto phase_group = [&](auto Gc) {
       constexpr int g = decltype(Gc)::value;
       if (SPLITR_KO & 8) return;
+      cplx Gg[GR];  // (SPLITR_GAHEAD) this group's G values, read a group ago; Gq takes the next group's
+      if constexpr (kGAhead) {
+        splitr_for<0, GR>([&](auto Ic) { Gg[decltype(Ic)::value] = Gq[decltype(Ic)::value]; });
+        if constexpr (SPLITR_GAHEAD == 1 && g > 0) {
+          g_fetch(splitr_c<(g > 0 ? g - 1 : 0)>{});
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
       if constexpr (g == NG - 1) Pg[g] = Bf;
       else Pg[g] = cm(Pg[g | (1 << splitr_low_clear(g))], F[splitr_low_clear(g)]);
       cplx Pt[GR];
@@ -484,11 +561,18 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
         if constexpr (rho == GR - 1) Pt[rho] = Pg[g];
         else Pt[rho] = cm(Pt[rho | (1 << splitr_low_clear(rho))], F[NW + splitr_low_clear(rho)]);
         constexpr int r = g | (rho << NW);
-        const cplx q = cm(Pt[rho], gval(splitr_c<r>{}));
+        cplx gv;
+        if constexpr (kGAhead) gv = Gg[rho];
+        else gv = gval(splitr_c<r>{});
+        const cplx q = cm(Pt[rho], gv);
         const double ax = xr[r], ay = xi[r];
         xr[r] = fma(ax, q.x, -ay * q.y);
         xi[r] = fma(ax, q.y, ay * q.x);
       });
+      if constexpr (kGAhead && SPLITR_GAHEAD == 2 && g > 0) {
+        g_fetch(splitr_c<(g > 0 ? g - 1 : 0)>{});
+        __builtin_amdgcn_sched_barrier(0);
+      }
     };
     constexpr bool kP5 = SPLITR_P5 && SPLITR_TMODE == 1 && NTB == 2 && NW > 0 && !(SPLITR_KO & 4);
     auto swap_d = [](double& a, double& c, auto is32) {
@@ -641,6 +725,39 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
     if constexpr (PLAIN_CLOSE) {
       splitr_for<0, NG>([&](auto Ic) { phase_group(splitr_c<(NG - 1 - decltype(Ic)::value)>{}); });
     } else {
+    // SPLITR_KWARM 2 / 3: the touches of the next stage's record are issued behind the phase factors of the LAST group - the
+    // last LDS read of the group loop is behind, the next wait on that counter is the one in front of the pass's first
+    // barrier; that group's rotations, pre(C0) and write_pre(C0, C1) lie in between - and are folded into `warm` only there.
+    // (Shapes whose groups go through the LDS transposition issue them behind the group loop.)  The address is the scalar
+    // c4 plus the stride; the touched values pass through an empty asm so that their use cannot be pulled forward.
+    unsigned wv[8];
+    constexpr bool kWarmLate = (SPLITR_KWARM == 2 || SPLITR_KWARM == 3) && !kP5 && NW > 0 && !(SPLITR_KO & 4);
+    // (complex drives issue them behind the loop too: <14, 5, DECAY, CPLX> spills a vector register otherwise)
+    constexpr bool kWarmInLoop = kWarmLate && SPLITR_TMODE == 1 && NTB == 2 && !CPLX;
+    auto warm_issue = [&]() {
+      const unsigned long long nv = (unsigned long long)c4 + (sg + 1 < n_stages ? stage_bytes : 0ull);
+      // (uniform by construction; the first-lane reads are free where the compiler already holds it in scalar registers
+      // and keep the asm's scalar constraint legal where it does not)
+      unsigned long long na = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(nv >> 32)) << 32) |
+                              (unsigned)__builtin_amdgcn_readfirstlane((int)nv);
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("" : "+s"(na));
+      if constexpr (SPLITR_KWARM == 2) {
+        typedef const __attribute__((address_space(4))) unsigned* uptr_t;
+        uptr_t nx = (uptr_t)na;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) wv[k] = nx[k < 7 ? 16 * k : 8 * N - 1];
+      } else {
+        // lane k on line k (the last line by its last word); the value of the PREVIOUS stage's touch is folded first
+        warm_va ^= warm_v;
+        const unsigned k = l & 7u;
+        // (the global address space by name: a generic pointer would make it a flat load, which counts on the LDS /
+        // scalar counter as well)
+        typedef const __attribute__((address_space(1))) unsigned* gptr_t;
+        warm_v = ((gptr_t)na)[k < 7u ? 16u * k : 8u * N - 1u];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    };
     constexpr int TMASK = SPLITR_TMODE == 2 ? 3 : 0;           // DPP lane bits rotated inside the transposition loop
     constexpr int PMASK = ((1 << ND) - 1) & ~TMASK;            // ... and with the pass chunks
     if constexpr (SPLITR_TMODE == 2) {
@@ -658,6 +775,7 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
       splitr_for<0, NG>([&](auto Ic) {
         constexpr int g = NG - 1 - decltype(Ic)::value;
         phase_group(splitr_c<g>{});
+        if constexpr (g == 0 && kWarmInLoop) warm_issue();
         rot_t_old(splitr_c<g>{});
         if constexpr (SPLITR_TMODE == 3) {
           // nothing to exchange
@@ -827,11 +945,19 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
       // (no barrier here: until the first one below a wave only touches its own slice of buffer 0 - the
       // transposition above and pass_write(0) - and buffer 0's last cross-wave reads, pass_read(2) of the previous
       // stage, sit before that stage's last barrier)
+      if constexpr (kWarmLate && !kWarmInLoop) warm_issue();
       pre(C0{});
       write_pre(C0{}, C1{});
+      if constexpr (SPLITR_KWARM == 2) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          asm volatile("" : "+s"(wv[k]));
+          warm ^= wv[k];
+        }
+      }
       __syncthreads();
       pass_read(C0{});
-      if (SPLITR_KWARM) {
+      if (SPLITR_KWARM == 1) {
         typedef const __attribute__((address_space(4))) unsigned* uptr_t;
         uptr_t nx = (uptr_t)(unsigned long long)(coefs + (size_t)(sg + 1 < n_stages ? sg + 1 : sg) * stage_stride);
 #pragma unroll
@@ -855,6 +981,7 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
     odd = !odd;
     }
     if (SPLITR_KWARM) asm volatile("" ::"s"(warm));
+    if constexpr (SPLITR_KWARM == 3) asm volatile("" ::"v"(warm_va));
   };
   const int n_full = R.kick_post == 0.0 ? n_stages - 1 : n_stages;
   if constexpr (SNAP) {
@@ -893,6 +1020,7 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
   } else {
     for (int sg = 0; sg < n_full; ++sg) stage(sg, std::false_type{});
   }
+  if (SPLITR_KWARM == 3) asm volatile("" ::"v"(warm_v));
   if (n_full < n_stages) stage(n_stages - 1, std::true_type{});
   // the layout is the odd one when an odd number of full stages ran
   // (tan form defers the product of a stage's cosines to the next stage's D; a run that closes on the kick has no next
