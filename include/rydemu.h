@@ -362,7 +362,8 @@ int ryd_general_mc_solve_many(ryd_handle** hs, int32_t n, void* const* states_de
  * 262144 = general path: the round-3 site kernel (k_gen_apply_sites) instead of the padded site tables of
  * k_gen_apply_fused (round 6),
  * 524288 = ryd_general_observe on density matrices: 5 columns of rho per chunk (the chunked path without a 1-GiB state);
- * ryd_general_observe_many: 5 evaluation times per chunk of tables (its chunked path without 256 MiB of them).
+ * ryd_general_observe_many, ryd_general_observe_density_many: 5 evaluation times per chunk of tables (their chunked path
+ * without 256 MiB of them).
  * Never needed for results. */
 int ryd_set_path(ryd_handle* h, int32_t force_generic);
 
@@ -514,6 +515,43 @@ int ryd_general_observe_many(ryd_handle* h, const void* states_dev, int32_t n_ti
                              int64_t stride_t, int64_t stride_b, const double* times, int32_t what,
                              int32_t local_dim, int32_t n_atoms, int32_t one_digit,
                              double* out_dev, void* stream);
+
+/* ryd_general_observe + RYD_OBS_DENSITY for every density matrix of a master-equation run on the general path (3-level
+ * "all" basis, leakage, XY mode, any effective noise) in one call: one memset and at most three launches per chunk of
+ * times, instead of one host copy, an SVD, one upload, a tiled transpose of the columns into scratch, two batched
+ * generator applications, two trace launches and a read-back per time.  A separate entry point:
+ * ryd_general_observe_many keeps refusing density matrices, ryd_observe_density_many general handles.
+ *   handle      a general-path KET handle (the V2 backend's noiseless engine: H(t) is the noiseless Hamiltonian).  A
+ *               two-level handle: RYD_ERR_INVALID.  A RYD_GENERAL_DENSITY handle: RYD_ERR_UNSUPPORTED.  local_dim,
+ *               n_atoms, one_digit as for ryd_general_observe; dim == D = local_dim^n_atoms <= 2^13, else RYD_ERR_INVALID.
+ *   states_dev  matrix (i, b) is row-major D x D, contiguous, starts at states_dev + i*stride_t + b*stride_b (strides in
+ *               complex128 elements, every offset 64-bit; both >= D*D, else RYD_ERR_INVALID) and is observed at times[i].
+ *   n_batch     matrices per time, any number >= 1: the handle's one problem serves every entry.
+ *   times       host float64[n_times] (us), in any order, repeats allowed, resolved as ryd_general_observe resolves its time.
+ *   what        the RYD_OBS_OCCUPATION / _CORRELATION / _ENERGY bits; a set RYD_OBS_DENSITY bit is ignored.
+ *   out_dev     float64[n_times][n_batch][N*N + N + 3], the layout of ryd_general_observe.  Zeroed first; slots not asked
+ *               for are exactly 0; the trace (slot N) is always written (by the pair launch, or by the energy kernel
+ *               when no pair launch runs).
+ * Launches: k_gen_obs_pairs on the diagonals of all matrices (when pair sums are asked for or no energy is) and, per
+ * chunk of times, k_gen_coefs_fused_many and k_gen_obs_energy_dm_many (k_general.hpp), which walks row r of G = -iH on
+ * COLUMN r of rho: Re Tr(H rho) = -Im sum_r (G rho)_rr from about D * L gathered elements, Re Tr(H^2 rho) =
+ * -Re sum_r (G G rho)_rr from D * L^2 (L padded table entries per row) - the D^2 elements of rho are never all read,
+ * nothing is transposed and no scratch grows with D^2.  rho is read as stored, neither rho nor H is assumed Hermitian,
+ * the real part is kept.  Agrees with ryd_general_observe + RYD_OBS_DENSITY within the sum of the two calls' rounding
+ * bounds (other summation order), not bit for bit.
+ * RYD_ERR_UNSUPPORTED: RYD_OBS_ENERGY on a handle with collapse operators (its generator is H_eff) and on a handle
+ * whose generator is not applied through the padded site tables (ryd_general_apply_path < 2).  The pair sums alone work
+ * on every ket handle.  n_times = 0 returns RYD_OK and touches nothing; n_batch < 1, n_times < 0 and null pointers with
+ * n_times > 0 are RYD_ERR_INVALID, a null handle before anything else.
+ * The time records, the tables of a chunk (256-MiB rule and ryd_set_path 524288 as for ryd_general_observe_many), the
+ * pinned upload buffer and its event are the scratch of ryd_general_observe_many: owned by the handle, grown on demand,
+ * freed with it.  The handle's own coefficient table, site matrices, work vector and the column scratch of
+ * ryd_general_observe are NOT written.  ryd_stats.n_applications does not move, n_launches counts the launches made.
+ * No host synchronisation except while the scratch grows.  One stream per handle, as for ryd_observe_many. */
+int ryd_general_observe_density_many(ryd_handle* h, const void* states_dev, int32_t n_times, int32_t n_batch,
+                                     int64_t stride_t, int64_t stride_b, const double* times, int32_t what,
+                                     int32_t local_dim, int32_t n_atoms, int32_t one_digit,
+                                     double* out_dev, void* stream);
 
 /* General-path handles: the kernel that the NEXT application of the generator runs with - 0 term by term (k_gen_apply),
  * 1 the site kernel, 2 the padded site tables (k_gen_apply_fused), 3 the same with the vector in LDS: the value that

@@ -133,6 +133,9 @@ SYMBOLS = {
                                       C.c_void_p, C.c_void_p]),
     "ryd_general_observe_many": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
                                            C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ryd_general_observe_density_many": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                                   C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                                   C.c_void_p]),
     "ryd_general_apply_path": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "ryd_ket_to_dm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ryd_outer_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

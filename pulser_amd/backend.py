@@ -1642,6 +1642,36 @@ def _observe_density_many_route(states: Sequence[Any], fires: Sequence[bool], en
     return _many_route(states, fires, engine, n_eigenstates, min_times, False, density=True)
 
 
+def _general_density_many_route(states: Sequence[Any], fires: Sequence[bool], engine: Any, n_eigenstates: int,
+                                min_times: int | None, energy: bool = True) -> tuple[Any, int, list[int]] | None:
+    """Which density matrices of one ``CoherentResults`` of a multi-level / XY master-equation run a single
+    ``GeneralEngine.observe_density_many`` call of ``engine`` serves (``QutipBackendV2.general_density_one_call``):
+    (store, sequence of the store, positions into ``states``), or None when the per-time path serves them all.  The
+    engine is what ``HamiltonianOperator.observe`` would serve a density matrix with: a ket ``GeneralEngine`` of batch 1
+    whose ``local_dim`` (2 - 4) is the number of eigenstates and whose dimension is ``local_dim ** n`` and, when the
+    energy moments are wanted (``energy``), one without collapse operators that applies its generator through the
+    padded site tables.  The states are unread ``LazyState`` matrices of one ``SnapshotStore`` whose tensor
+    ``[times, sequences, dim, dim]`` is still on the GPU (``_walk_store``); at least
+    ``max(min_times, QutipBackendV2._GENERAL_DENSITY_OBSERVE_MANY_FLOOR)`` positions must qualify (None: the path is
+    off).  ``_many_route`` and its two callers answer as before: this is a predicate of its own."""
+    if min_times is None or engine is None or not hasattr(engine, "local_dim"):
+        return None
+    if not hasattr(engine, "observe_density_many"):
+        return None
+    d = int(engine.local_dim)
+    if (getattr(engine, "is_density", False) or getattr(engine, "batch", 0) != 1 or not 2 <= d <= 4
+            or d != n_eigenstates or d ** int(engine.n) != engine.dim):
+        return None
+    if energy:
+        apply_path = getattr(engine, "apply_path", None)
+        if getattr(engine, "n_collapse", 0) or apply_path is None or apply_path() not in ("fused", "fused_lds"):
+            return None
+    store, b, positions, _ = _walk_store(states, fires, (int(engine.dim), int(engine.dim)))
+    if store is None or len(positions) < max(int(min_times), QutipBackendV2._GENERAL_DENSITY_OBSERVE_MANY_FLOOR):
+        return None
+    return store, b, positions
+
+
 def _overlap_many_route(states: Sequence[Any], fires: Sequence[bool],
                         min_times: int | None) -> tuple[Any, int, list[int], bool] | None:
     """Which states of one ``CoherentResults`` the device calls behind ``Fidelity`` / ``Expectation``
@@ -1708,6 +1738,15 @@ class QutipBackendV2:
     # (QutipEmulator.run(mc_ensemble=True)): d^N numbers per trajectory, no 16-GiB cap on the evaluation times.  Values
     # agree with the default route's within rounding, not bit for bit; every other run is left exactly as it is.
     mc_ensemble: bool = False
+    # True: the density matrices of a multi-level / XY master-equation run (3-level "all" basis, leakage, XY mode, any
+    # eff_noise) stay on the device (QutipEmulator.run(general_density_snapshots=True)) and their occupations,
+    # correlations and energy moments come from ONE GeneralEngine.observe_density_many call per distinct one-state, from
+    # max(observe_many_min_times, the floor below) firing evaluation times on; Fidelity and Expectation then take their
+    # own one-call route on the same store.  Values are divided by the device trace where the default route divides by
+    # the trace norm of an SVD: they agree within the rounding bounds, not bit for bit.  Set on an instance, like
+    # mc_ensemble; not a QutipConfig key.  False: no code path differs.
+    general_density_one_call: bool = False
+    _GENERAL_DENSITY_OBSERVE_MANY_FLOOR = 128
 
     def __init__(self, sequence: Any, *, config: QutipConfig | None = None,
                  mimic_qpu: bool = False) -> None:
@@ -1759,7 +1798,8 @@ class QutipBackendV2:
 
     def run(self) -> Results:
         return self._run_raw(self._sim_obj, self._config, dict(self._options),
-                             observe_many_min_times=self.observe_many_min_times, mc_ensemble=self.mc_ensemble)
+                             observe_many_min_times=self.observe_many_min_times, mc_ensemble=self.mc_ensemble,
+                             general_density_one_call=self.general_density_one_call)
 
     @staticmethod
     def run_from_sequence_samples(sequence_samples: Any, register: Any = None, device: Any = None,
@@ -1774,10 +1814,13 @@ class QutipBackendV2:
 
     @staticmethod
     def _run_raw(sim: QutipEmulator, config: QutipConfig, options: dict[str, Any], *,
-                 observe_many_min_times: Any = "class", mc_ensemble: bool = False) -> Results:
+                 observe_many_min_times: Any = "class", mc_ensemble: bool = False,
+                 general_density_one_call: bool = False) -> Results:
         """``observe_many_min_times``: the threshold of the one-call observable path for this run (``run`` passes the
         instance's, so a subclass or an instance may set its own); by default the class attribute.  ``mc_ensemble``:
-        the instance's ``QutipBackendV2.mc_ensemble``; it takes effect where ``_mc_ensemble_route`` allows."""
+        the instance's ``QutipBackendV2.mc_ensemble``; it takes effect where ``_mc_ensemble_route`` allows.
+        ``general_density_one_call``: the instance's attribute of that name; it takes effect on a multi-level / XY
+        master-equation run with enough firing evaluation times."""
         from .engine import Engine, GeneralEngine
         from .general import lower_general
         from .terms import SUPPORTED_BASES
@@ -1875,6 +1918,16 @@ class QutipBackendV2:
             firing = sum(any(o._fires(config, float(t / (T * 1e-3)), T) for o in on_kets) for t in sim._eval_times_array)
             if firing >= max(int(min_times), QutipBackendV2._OVERLAP_MANY_FLOOR):
                 options = {**options, "general_device_snapshots": True}
+        if general_density_one_call and min_times is not None and hdata.collapse_ops()[0] and (
+                hdata.basis_name not in SUPPORTED_BASES or len(hdata.eigenbasis) != 2 or hdata.interaction_type == "XY"):
+            # a master-equation run of the general path (general_kets() WITH collapse operators): the density matrices
+            # stay on the device when enough evaluation times carry an observable that a one-call route serves
+            served = watching + [o for o in overlap_watchers if o not in watching]
+            firing = sum(any(o._fires(config, float(t / (T * 1e-3)), T) for o in served) for t in sim._eval_times_array)
+            if firing >= max(int(min_times), QutipBackendV2._GENERAL_DENSITY_OBSERVE_MANY_FLOOR):
+                options = {**options, "general_density_snapshots": True}
+                # (the energy moments need the padded site tables, as on the ket route)
+                general_one_call = general_one_call or (wants_energy and bool(watching))
         overlap_cache: dict[str, Any] = {}  # like many_cache, for overlapped_many
         if mc_ensemble and _mc_ensemble_route(sim, config):
             # the energy moments of the trajectories are those of the H(t) every HamiltonianOperator below wraps (the
@@ -1953,6 +2006,11 @@ class QutipBackendV2:
             density = route is None  # no kets to serve: the density matrices of a two-level master-equation run?
             if density:
                 route = _observe_density_many_route([r.state for r in rs], fires, eng, len(eigenstates), min_times)
+            general_dm = False  # ... or those of a multi-level / XY one (QutipBackendV2.general_density_one_call)?
+            if route is None and general_density_one_call:
+                route = _general_density_many_route([r.state for r in rs], fires, eng, len(eigenstates), min_times,
+                                                    wants_energy)
+                general_dm = route is not None
             if route is None:
                 return {}
             store, b, positions = route
@@ -1970,7 +2028,10 @@ class QutipBackendV2:
                 if dev is None:  # spilled since the route was taken
                     return {}
                 x = snapshots(dev, idx)  # every time, or every k-th: a view, observed in place
-                if density:
+                if general_dm:  # (as for the kets: only the first call carries the energy moments)
+                    got = {d: eng.observe_density_many(x, times_us, one=d, energy=wants_energy and k == 0)
+                           for k, d in enumerate(digits)}
+                elif density:
                     got = {0: eng.observe_density_many(x, times_us, energy=wants_energy)}
                 elif hasattr(eng, "local_dim"):  # (only the first call carries the energy moments)
                     got = {d: eng.observe_many(x, times_us, one=d, energy=wants_energy and k == 0)

@@ -183,11 +183,12 @@ struct ryd_handle {
   // ryd_general_observe with RYD_OBS_DENSITY: the staged columns of rho and H applied to them (allocated on first use)
   cplx* gen_obs_scratch = nullptr;
   size_t gen_obs_scratch_bytes = 0;
-  bool gen_obs_small_chunks = false;  // test hook: 5 columns per chunk
-  // The scratch of ryd_observe_many, ryd_observe_density_many and ryd_general_observe_many (obs_many_stage_times), grown
+  bool gen_obs_small_chunks = false;  // test hook: 5 columns per chunk (ryd_general_observe), 5 times per chunk (the *_many calls)
+  // The scratch of ryd_observe_many, ryd_observe_density_many, ryd_general_observe_many and
+  // ryd_general_observe_density_many (obs_many_stage_times), grown
   // on demand: [n_times] ObsManyTime, then the caller's table, and the pinned host copy of the former with the event that
-  // says its last upload has been read.  Table of the two Ising calls: coefficients [n_times][B][N][4]; of the general
-  // call (a general handle never takes the other two): tcoef[n_terms] and mvals[E + Dg] per time
+  // says its last upload has been read.  Table of the two Ising calls: coefficients [n_times][B][N][4]; of the two general
+  // calls (a general handle never takes the other two): tcoef[n_terms] and mvals[E + Dg] per time
   void* obs_many_dev = nullptr;
   size_t obs_many_bytes = 0;
   ObsManyTime* obs_many_pin = nullptr;

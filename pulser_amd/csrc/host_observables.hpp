@@ -214,7 +214,7 @@ static int obs_many_coef_table(ryd_handle* h, int n_times, const double* times, 
   return RYD_OK;
 }
 
-// What the three *_many calls share once the handle is known to be theirs.  obs_many_front refuses the shapes (`who`
+// What the four *_many calls share once the handle is known to be theirs.  obs_many_front refuses the shapes (`who`
 // opens every message; one state is a ket of D amplitudes or, with `dm`, a matrix of D * D elements; an Ising handle of
 // batch B serves B states per time, or any number when B is 1), answers RYD_OK with n_states == 0 to a call without
 // times, zeroes the output [n_states][N*N+N+3] on the caller's stream and settles the pair kernel's launch.  A
@@ -322,6 +322,83 @@ extern "C" int ryd_observe_density_many(ryd_handle* h, const void* states_dev, i
   return ising_observe_many(h, true, states_dev, n_times, n_batch, stride_t, stride_b, times, what, out_dev, stream);
 }
 
+// The energy moments of ryd_general_observe_many (kets, k_gen_obs_energy_many) and ryd_general_observe_density_many (`dm`:
+// D x D matrices, k_gen_obs_energy_dm_many) after obs_many_front: per chunk of times one table launch and one energy launch.
+static int gen_obs_many_energy(ryd_handle* h, bool dm, const ObsManyFront& f, int64_t D, int N, const void* states_dev,
+                               int32_t n_times, int32_t n_batch, int64_t stride_t, int64_t stride_b, const double* times,
+                               double* out_dev) {
+  int rc;
+  const hipStream_t st = f.st;
+  const int stride = f.stride;
+  // (interval, offset) of every time on the host; per time tcoef[n_terms] and mvals[E + Dg] in the handle's scratch (the
+  // handle's own gen_tcoef / gen_fused.mvals / wA are not written).  Calls on one handle are ordered by using ONE stream.
+  const GenFusedDev& F = h->gen_fused;
+  const int n_terms = (int)h->gen_host.size();
+  const size_t per_time = (size_t)(n_terms + F.E + F.Dg);
+  size_t chunk = std::max<size_t>(kGenObsScratchCap / (per_time * sizeof(cplx)), 1);
+  if (h->gen_obs_small_chunks) chunk = std::min<size_t>(chunk, 5);
+  chunk = std::min<size_t>(chunk, (size_t)n_times);
+  ObsManyTime* tm_dev = nullptr;
+  cplx* table = nullptr;
+  if ((rc = obs_many_stage_times(h, n_times, times, chunk * per_time * sizeof(cplx), st, &tm_dev, (void**)&table))) return rc;
+  {
+    static bool attr[64] = {};
+    const int dev = h->cfg.device;
+    if (dev < 0 || dev >= 64 || !attr[dev]) {
+      HIPCHK(hipFuncSetAttribute((const void*)k_gen_obs_energy_many<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      HIPCHK(hipFuncSetAttribute((const void*)k_gen_obs_energy_many<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      HIPCHK(hipFuncSetAttribute((const void*)k_gen_obs_energy_dm_many, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      if (dev >= 0 && dev < 64) attr[dev] = true;
+    }
+  }
+  GenObsManyArgs A;
+  A.terms = h->gen_terms_dev;
+  A.diag_terms = h->gen_diag_terms_dev;
+  for (int k = 0; k < 4; ++k) {
+    const bool have = k < h->gen_n_diag;
+    A.diag_idx[k] = have ? h->gen_diag_host[k] : 0;
+    A.diag_val[k] = have ? h->gen_host[h->gen_diag_host[k]].dev.val : nullptr;
+  }
+  A.F = F;
+  A.stride_t = stride_t;
+  A.stride_b = stride_b;
+  A.dim = (long long)D;
+  A.n_batch = n_batch;
+  A.n_terms = n_terms;
+  A.n_diag = h->gen_n_diag;
+  A.d = h->gen_d;
+  A.n_dig = h->gen_ndig;
+  A.with_norm = f.pairs ? 0 : 1;
+  A.out_stride = stride;
+  A.off = N * N + N + 1;
+  A.norm_off = N;
+  A.table = table;
+  // kets: the application's LDS image and a second buffer for the waves' partial sums (<= 150 KiB + 8 KiB of the CU's 160).
+  // matrices: the tables, three partial sums of three waves, the row offsets (the application's image without the vector + 1 KiB)
+  const size_t lds = dm ? (size_t)(F.E + F.Dg) * sizeof(cplx) + 3 * GEN_FUSED_ROWS * 3 * sizeof(cplx) +
+                              (size_t)((F.E + 3) & ~3) * sizeof(int)
+                        : h->gen_fused_lds + 4 * GEN_FUSED_ROWS * 2 * sizeof(cplx);
+  const unsigned n_rb = (unsigned)((D + GEN_FUSED_ROWS - 1) / GEN_FUSED_ROWS);
+  const unsigned gx = (n_rb + GEN_OBS_ROW_BLOCKS - 1) / GEN_OBS_ROW_BLOCKS;
+  for (size_t t0 = 0; t0 < (size_t)n_times; t0 += chunk) {  // (one chunk unless the tables exceed kGenObsScratchCap)
+    const size_t nt = std::min<size_t>(chunk, (size_t)n_times - t0);
+    hipLaunchKernelGGL(k_gen_coefs_fused_many, dim3((unsigned)nt), dim3(256), 0, st, (const cplx*)h->pp_dev, h->n_knots - 1,
+                       (const int*)h->gen_series_dev, (const int*)h->gen_conj_dev, (const cplx*)h->gen_scale_dev, n_terms,
+                       (const ObsManyTime*)(tm_dev + t0), table, F);
+    HIPCHK(hipGetLastError());
+    A.states = (const cplx*)states_dev + (long long)t0 * stride_t;
+    A.n_states = (long long)nt * n_batch;
+    A.out = out_dev + t0 * (size_t)n_batch * stride;
+    const dim3 grid(gx, (unsigned)std::min<long long>(A.n_states, 65535));
+    if (dm) hipLaunchKernelGGL(k_gen_obs_energy_dm_many, grid, dim3(256), lds, st, A);
+    else if (h->gen_fused_xlds) hipLaunchKernelGGL(k_gen_obs_energy_many<true>, grid, dim3(256), lds, st, A);
+    else hipLaunchKernelGGL(k_gen_obs_energy_many<false>, grid, dim3(256), lds, st, A);
+    HIPCHK(hipGetLastError());
+    h->stats.n_launches += 2;
+  }
+  return RYD_OK;
+}
+
 // ryd_general_observe for every evaluation time of a run (kets of a general-path handle): k_gen_obs_pairs,
 // k_gen_coefs_fused_many and k_gen_obs_energy_many (k_general.hpp)
 extern "C" int ryd_general_observe_many(ryd_handle* h, const void* states_dev, int32_t n_times, int32_t n_batch,
@@ -350,78 +427,54 @@ extern "C" int ryd_general_observe_many(ryd_handle* h, const void* states_dev, i
   rc = obs_many_front(h, "general observe_many", false, D, N, n_times, n_batch, stride_t, stride_b, states_dev, times, what,
                       out_dev, stream, &f);
   if (rc || !f.n_states) return rc;
-  const hipStream_t st = f.st;
-  const int stride = f.stride;
   if (f.pairs) {
-    hipLaunchKernelGGL(k_gen_obs_pairs, dim3((unsigned)((D + 2047) / 2048), f.gy), dim3(256), 0, st,
+    hipLaunchKernelGGL(k_gen_obs_pairs, dim3((unsigned)((D + 2047) / 2048), f.gy), dim3(256), 0, f.st,
                        (const cplx*)states_dev, f.n_states, (int)n_batch, (long long)stride_t, (long long)stride_b,
-                       (unsigned)D, N, (int)local_dim, (int)one_digit, 0, (int)what, out_dev, stride);
+                       (unsigned)D, N, (int)local_dim, (int)one_digit, 0, (int)what, out_dev, f.stride);
     HIPCHK(hipGetLastError());
     h->stats.n_launches++;
   }
   if (!(what & RYD_OBS_ENERGY)) return RYD_OK;
-  // (interval, offset) of every time on the host; per time tcoef[n_terms] and mvals[E + Dg] in the handle's scratch (the
-  // handle's own gen_tcoef / gen_fused.mvals / wA are not written).  Calls on one handle are ordered by using ONE stream.
-  const GenFusedDev& F = h->gen_fused;
-  const int n_terms = (int)h->gen_host.size();
-  const size_t per_time = (size_t)(n_terms + F.E + F.Dg);
-  size_t chunk = std::max<size_t>(kGenObsScratchCap / (per_time * sizeof(cplx)), 1);
-  if (h->gen_obs_small_chunks) chunk = std::min<size_t>(chunk, 5);
-  chunk = std::min<size_t>(chunk, (size_t)n_times);
-  ObsManyTime* tm_dev = nullptr;
-  cplx* table = nullptr;
-  if ((rc = obs_many_stage_times(h, n_times, times, chunk * per_time * sizeof(cplx), st, &tm_dev, (void**)&table))) return rc;
-  {
-    static bool attr[64] = {};
-    const int dev = h->cfg.device;
-    if (dev < 0 || dev >= 64 || !attr[dev]) {
-      HIPCHK(hipFuncSetAttribute((const void*)k_gen_obs_energy_many<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gen_obs_energy_many<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      if (dev >= 0 && dev < 64) attr[dev] = true;
-    }
+  return gen_obs_many_energy(h, false, f, D, N, states_dev, n_times, n_batch, stride_t, stride_b, times, out_dev);
+}
+
+// ryd_general_observe + RYD_OBS_DENSITY for every density matrix of a master-equation run on the general path:
+// k_gen_obs_pairs on the diagonals, k_gen_coefs_fused_many and k_gen_obs_energy_dm_many (k_general.hpp)
+extern "C" int ryd_general_observe_density_many(ryd_handle* h, const void* states_dev, int32_t n_times, int32_t n_batch,
+                                                int64_t stride_t, int64_t stride_b, const double* times, int32_t what,
+                                                int32_t local_dim, int32_t n_atoms, int32_t one_digit, double* out_dev,
+                                                void* stream) {
+  const char* who = "general observe_density_many";
+  if (!h) return fail(RYD_ERR_INVALID, "%s: null handle", who);
+  if (!h->general) return fail(RYD_ERR_INVALID, "%s: not a general-path handle: use ryd_observe_density_many", who);
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (local_dim < 2 || local_dim > 4 || n_atoms < 1 || n_atoms > 26 || one_digit < 0 || one_digit >= local_dim)
+    return fail(RYD_ERR_INVALID, "%s: local_dim=%d n_atoms=%d one_digit=%d out of range", who, local_dim, n_atoms, one_digit);
+  if (h->gen_density)
+    return fail(RYD_ERR_UNSUPPORTED, "%s: matrices on a ket handle only; a RYD_GENERAL_DENSITY handle observes vec(rho) with ryd_general_observe", who);
+  int64_t D = 1;
+  for (int i = 0; i < n_atoms; ++i) {
+    D *= local_dim;
+    if (D > ((int64_t)1 << 13))
+      return fail(RYD_ERR_INVALID, "%s: a %d^%d x %d^%d density matrix exceeds 2^26 entries", who, local_dim, n_atoms, local_dim, n_atoms);
   }
-  GenObsManyArgs A;
-  A.terms = h->gen_terms_dev;
-  A.diag_terms = h->gen_diag_terms_dev;
-  for (int k = 0; k < 4; ++k) {
-    const bool have = k < h->gen_n_diag;
-    A.diag_idx[k] = have ? h->gen_diag_host[k] : 0;
-    A.diag_val[k] = have ? h->gen_host[h->gen_diag_host[k]].dev.val : nullptr;
-  }
-  A.F = F;
-  A.stride_t = stride_t;
-  A.stride_b = stride_b;
-  A.dim = (long long)D;
-  A.n_batch = n_batch;
-  A.n_terms = n_terms;
-  A.n_diag = h->gen_n_diag;
-  A.d = h->gen_d;
-  A.n_dig = h->gen_ndig;
-  A.with_norm = f.pairs ? 0 : 1;
-  A.out_stride = stride;
-  A.off = N * N + N + 1;
-  A.norm_off = N;
-  A.table = table;
-  // the application's LDS image and a second buffer for the waves' partial sums (<= 150 KiB + 8 KiB of the CU's 160)
-  const size_t lds = h->gen_fused_lds + 4 * GEN_FUSED_ROWS * 2 * sizeof(cplx);
-  const unsigned n_rb = (unsigned)((D + GEN_FUSED_ROWS - 1) / GEN_FUSED_ROWS);
-  const unsigned gx = (n_rb + GEN_OBS_ROW_BLOCKS - 1) / GEN_OBS_ROW_BLOCKS;
-  for (size_t t0 = 0; t0 < (size_t)n_times; t0 += chunk) {  // (one chunk unless the tables exceed kGenObsScratchCap)
-    const size_t nt = std::min<size_t>(chunk, (size_t)n_times - t0);
-    hipLaunchKernelGGL(k_gen_coefs_fused_many, dim3((unsigned)nt), dim3(256), 0, st, (const cplx*)h->pp_dev, h->n_knots - 1,
-                       (const int*)h->gen_series_dev, (const int*)h->gen_conj_dev, (const cplx*)h->gen_scale_dev, n_terms,
-                       (const ObsManyTime*)(tm_dev + t0), table, F);
+  if ((int64_t)h->dim != D)
+    return fail(RYD_ERR_INVALID, "%s: dim %lld is not %d^%d", who, (long long)h->dim, local_dim, n_atoms);
+  const int N = n_atoms;
+  what &= ~RYD_OBS_DENSITY;
+  ObsManyFront f;
+  rc = obs_many_front(h, who, true, D, N, n_times, n_batch, stride_t, stride_b, states_dev, times, what, out_dev, stream, &f);
+  if (rc || !f.n_states) return rc;
+  if (f.pairs) {
+    hipLaunchKernelGGL(k_gen_obs_pairs, dim3((unsigned)((D + 2047) / 2048), f.gy), dim3(256), 0, f.st,
+                       (const cplx*)states_dev, f.n_states, (int)n_batch, (long long)stride_t, (long long)stride_b,
+                       (unsigned)D, N, (int)local_dim, (int)one_digit, 1, (int)what, out_dev, f.stride);
     HIPCHK(hipGetLastError());
-    A.states = (const cplx*)states_dev + (long long)t0 * stride_t;
-    A.n_states = (long long)nt * n_batch;
-    A.out = out_dev + t0 * (size_t)n_batch * stride;
-    const dim3 grid(gx, (unsigned)std::min<long long>(A.n_states, 65535));
-    if (h->gen_fused_xlds) hipLaunchKernelGGL(k_gen_obs_energy_many<true>, grid, dim3(256), lds, st, A);
-    else hipLaunchKernelGGL(k_gen_obs_energy_many<false>, grid, dim3(256), lds, st, A);
-    HIPCHK(hipGetLastError());
-    h->stats.n_launches += 2;
+    h->stats.n_launches++;
   }
-  return RYD_OK;
+  if (!(what & RYD_OBS_ENERGY)) return RYD_OK;
+  return gen_obs_many_energy(h, true, f, D, N, states_dev, n_times, n_batch, stride_t, stride_b, times, out_dev);
 }
 
 extern "C" int ryd_ket_to_dm(ryd_handle* h, const void* psi_dev, void* rho_dev, void* stream) {

@@ -285,19 +285,22 @@ struct GenFusedArgs {
 // the four partial sums meet in LDS.  (First version, one row per thread and all sites per row: the 78 sites of a 12-atom
 // XY register read 5.9 KB of LDS per row - 16 workgroups, LDS-bandwidth-bound at 10 - 14 us; a 3-level register of 9
 // atoms ran 9 sites in series on 77 CUs.)  Site descriptors are wave-uniform: scalar loads from global memory, not LDS.
-template <int K>
+// NW: the waves that split the sites (4; 1 = this wave takes them all).  COL: `x` is a column of a row-major matrix with
+// `mul` elements per row - entry i is x[i * mul]; without it `mul` is not read and the code is what it was.
+template <int K, int NW = 4, bool COL = false>
 __device__ __forceinline__ void gen_fused_sites(const GenSiteF* __restrict__ sites, int s0, int s1, int wave,
                                                 const cplx* __restrict__ mv, const cplx* __restrict__ mvd,
                                                 const int* __restrict__ dl, const cplx* __restrict__ x, int row,
-                                                unsigned long long digits, unsigned mask, int kdyn, cplx& acc, cplx& dsum) {
+                                                unsigned long long digits, unsigned mask, int kdyn, cplx& acc, cplx& dsum,
+                                                int mul = 1) {
   if constexpr (K > 0) {
     constexpr int UNR = K <= 2 ? 4 : 2;  // sites in flight per wave (x 4 waves)
-    for (int sb = s0 + wave; sb < s1; sb += 4 * UNR) {
+    for (int sb = s0 + wave; sb < s1; sb += NW * UNR) {
       cplx mvv[UNR * K], xv[UNR * K];
 #pragma unroll
       for (int u = 0; u < UNR; ++u) {
-        const bool on = sb + 4 * u < s1;
-        const int s = on ? sb + 4 * u : sb;
+        const bool on = sb + NW * u < s1;
+        const int s = on ? sb + NW * u : sb;
         const GenSiteF si = sites[s];  // (s is wave-uniform: scalar loads)
         const int R = (int)((digits >> si.shift0) & mask) * si.mul + (int)((digits >> si.shift1) & (unsigned)si.mask1);
         const cplx dg = mvd[si.diag_off + R];
@@ -308,14 +311,14 @@ __device__ __forceinline__ void gen_fused_sites(const GenSiteF* __restrict__ sit
         for (int k = 0; k < K; ++k) {
           const cplx m = mv[e0 + k];
           mvv[u * K + k] = on ? m : make_double2(0.0, 0.0);
-          xv[u * K + k] = x[row + dl[e0 + k]];
+          xv[u * K + k] = x[COL ? (row + dl[e0 + k]) * mul : row + dl[e0 + k]];
         }
       }
 #pragma unroll
       for (int j = 0; j < UNR * K; ++j) acc = cfma(mvv[j], xv[j], acc);
     }
   } else {  // (K > 4: a dense two-digit superoperator)
-    for (int s = s0 + wave; s < s1; s += 4) {
+    for (int s = s0 + wave; s < s1; s += NW) {
       const GenSiteF si = sites[s];
       const int R = (int)((digits >> si.shift0) & mask) * si.mul + (int)((digits >> si.shift1) & (unsigned)si.mask1);
       const cplx dg = mvd[si.diag_off + R];
@@ -323,32 +326,33 @@ __device__ __forceinline__ void gen_fused_sites(const GenSiteF* __restrict__ sit
       dsum.y += dg.y;
       const int e0 = si.ent_off + R * kdyn;
 #pragma unroll 4
-      for (int k = 0; k < kdyn; ++k) acc = cfma(mv[e0 + k], x[row + dl[e0 + k]], acc);
+      for (int k = 0; k < kdyn; ++k) acc = cfma(mv[e0 + k], x[COL ? (row + dl[e0 + k]) * mul : row + dl[e0 + k]], acc);
     }
   }
 }
 
 // Every site group of one row for this wave: acc += off-diagonal entries x gathered amplitudes, dsum += site diagonals
-// (k_gen_apply_fused, and k_gen_obs_energy_many for the same value of the row)
+// (k_gen_apply_fused, and k_gen_obs_energy_many / k_gen_obs_energy_dm_many for the same value of the row)
+template <int NW = 4, bool COL = false>
 __device__ __forceinline__ void gen_fused_row(const GenFusedDev& F, int wave, const cplx* __restrict__ mv,
                                               const cplx* __restrict__ mvd, const int* __restrict__ dl,
                                               const cplx* __restrict__ x, int row, unsigned long long digits, unsigned mask,
-                                              cplx& acc, cplx& dsum) {
+                                              cplx& acc, cplx& dsum, int mul = 1) {
   const GenSiteF* __restrict__ sites = F.sites;
   for (int g = 0; g < F.n_groups; ++g) {
     const int K = F.gK[g], s0 = F.gBegin[g], s1 = F.gEnd[g];
     switch (K) {
-      case 0: for (int s = s0 + wave; s < s1; s += 4) {  // diagonal-only sites
+      case 0: for (int s = s0 + wave; s < s1; s += NW) {  // diagonal-only sites
                 const GenSiteF si = sites[s];
                 const int R = (int)((digits >> si.shift0) & mask) * si.mul + (int)((digits >> si.shift1) & (unsigned)si.mask1);
                 const cplx dg = mvd[si.diag_off + R];
                 dsum.x += dg.x; dsum.y += dg.y;
               } break;
-      case 1: gen_fused_sites<1>(sites, s0, s1, wave, mv, mvd, dl, x, row, digits, mask, K, acc, dsum); break;
-      case 2: gen_fused_sites<2>(sites, s0, s1, wave, mv, mvd, dl, x, row, digits, mask, K, acc, dsum); break;
-      case 3: gen_fused_sites<3>(sites, s0, s1, wave, mv, mvd, dl, x, row, digits, mask, K, acc, dsum); break;
-      case 4: gen_fused_sites<4>(sites, s0, s1, wave, mv, mvd, dl, x, row, digits, mask, K, acc, dsum); break;
-      default: gen_fused_sites<0>(sites, s0, s1, wave, mv, mvd, dl, x, row, digits, mask, K, acc, dsum); break;
+      case 1: gen_fused_sites<1, NW, COL>(sites, s0, s1, wave, mv, mvd, dl, x, row, digits, mask, K, acc, dsum, mul); break;
+      case 2: gen_fused_sites<2, NW, COL>(sites, s0, s1, wave, mv, mvd, dl, x, row, digits, mask, K, acc, dsum, mul); break;
+      case 3: gen_fused_sites<3, NW, COL>(sites, s0, s1, wave, mv, mvd, dl, x, row, digits, mask, K, acc, dsum, mul); break;
+      case 4: gen_fused_sites<4, NW, COL>(sites, s0, s1, wave, mv, mvd, dl, x, row, digits, mask, K, acc, dsum, mul); break;
+      default: gen_fused_sites<0, NW, COL>(sites, s0, s1, wave, mv, mvd, dl, x, row, digits, mask, K, acc, dsum, mul); break;
     }
   }
 }
@@ -557,6 +561,143 @@ __global__ __launch_bounds__(256) void k_gen_obs_energy_many(const GenObsManyArg
     }
     // (every wave has passed the last row block's barrier after its last read of `mv` and `xs`: they may be staged again;
     // the partial sums wave 0 may still be reading are not touched before the next staging barrier)
+  }
+}
+
+// ---------------------------------------------------------------------------
+// ryd_general_observe_density_many: Re Tr(H rho) and Re Tr(H^2 rho) of the density matrices of EVERY evaluation time of
+// a master-equation run, from the entries of rho that H and H^2 reach - no transpose, no scratch of the size of rho.
+// ---------------------------------------------------------------------------
+// With G = -iH of the time's tables,
+//     Re Tr(H rho) = -Im sum_r (G rho)_rr,      Re Tr(H^2 rho) = -Re sum_r (G G rho)_rr.
+// Lane r of a 64-row block works on COLUMN r of the row-major matrix, x_c = rho[c * D + r] (gen_fused_row<.., COL>: the
+// same site walk with the index multiplied by D; rows of rho are contiguous, so the 64 lanes of a gather with equal row
+// offsets read 64 neighbouring elements of one row of rho).  rho is read as stored, neither it nor H assumed Hermitian.
+//   y_r = (G rho)_rr      one row evaluation, the four waves splitting the sites exactly as the application does;
+//   (G G rho)_rr          the same outer walk over row r of G with every gathered value replaced by
+//                         y_c = (G rho_{:,r})_c at c = r + delta: an all-sites row evaluation by the wave that owns the
+//                         outer site (gen_fused_row<1, COL>) plus the dense diagonal terms at c.  The diagonal of G
+//                         takes y_r itself, which wave 0 has after the reduction.
+// About D * L gathers for the first moment and D * L^2 for the second (L padded entries per row; padding, value 0, is
+// skipped in the outer walk), against D^2 * L for two applications on all columns.  Wave 0 keeps -Im y_r, -Re(GG rho)_rr
+// (and Re rho_rr when no pair launch ran) in registers across its row blocks, reduces with __shfl_down and issues one
+// fp64 atomicAdd per sum, workgroup and state.  Arguments, tables, state addressing and the grid are those of
+// k_gen_obs_energy_many (A.dim = D, one state = D * D elements); every index fits int (D * D <= 2^26).
+__device__ __forceinline__ cplx gen_dm_col_entry(const GenObsManyArgs& A, const cplx* __restrict__ tc,
+                                                 const cplx* __restrict__ mv, const cplx* __restrict__ mvd,
+                                                 const int* __restrict__ dl, const cplx* __restrict__ x, int c, unsigned mask,
+                                                 int D) {
+  cplx a = make_double2(0.0, 0.0), ds = make_double2(0.0, 0.0);
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (k < A.n_diag) ds = cfma(tc[A.diag_idx[k]], A.diag_val[k][c], ds);
+  for (int k = 4; k < A.n_diag; ++k) {
+    const int t = A.diag_terms[k];
+    ds = cfma(tc[t], A.terms[t].val[c], ds);
+  }
+  const unsigned long long digits = gen_pack_digits(c, A.d, A.n_dig);
+  gen_fused_row<1, true>(A.F, 0, mv, mvd, dl, x, c, digits, mask, a, ds, D);
+  return cfma(ds, x[c * D], a);
+}
+
+__global__ __launch_bounds__(256) void k_gen_obs_energy_dm_many(const GenObsManyArgs A) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int E = A.F.E, Dg = A.F.Dg;
+  cplx* mv = reinterpret_cast<cplx*>(smem);                              // [E] off-diagonal, [Dg] diagonal
+  cplx* mvd = mv + E;
+  cplx* red = mvd + Dg;                                                  // [3][64][3]: partial sums of waves 1 - 3
+  int* dl = reinterpret_cast<int*>(red + 3 * GEN_FUSED_ROWS * 3);        // [E]
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int D = (int)A.dim;
+  const int n_rb = (D + GEN_FUSED_ROWS - 1) / GEN_FUSED_ROWS;
+  const int rb0 = blockIdx.x * GEN_OBS_ROW_BLOCKS;
+  const int rb1 = rb0 + GEN_OBS_ROW_BLOCKS < n_rb ? rb0 + GEN_OBS_ROW_BLOCKS : n_rb;
+  const unsigned mask = A.d <= 4 ? 3u : 15u;
+  const int per_time = A.n_terms + E + Dg;
+  const GenSiteF* __restrict__ sites = A.F.sites;
+  for (int i = threadIdx.x; i < E; i += 256) dl[i] = A.F.delta[i];
+  for (long long s = blockIdx.y; s < A.n_states; s += gridDim.y) {
+    const long long it = s / A.n_batch, b = s - it * A.n_batch;
+    const cplx* __restrict__ rho = A.states + it * A.stride_t + b * A.stride_b;
+    const cplx* __restrict__ tc = A.table + (size_t)it * per_time;
+    const cplx* __restrict__ mg = tc + A.n_terms;
+    for (int i = threadIdx.x; i < E + Dg; i += 256) mv[i] = mg[i];
+    __syncthreads();
+    double e1 = 0.0, e2 = 0.0, tr = 0.0;
+    for (int rb = rb0; rb < rb1; ++rb) {
+      const int row = rb * GEN_FUSED_ROWS + lane;
+      const bool live = row < D;
+      cplx xr = make_double2(0.0, 0.0), dsum = make_double2(0.0, 0.0), acc = make_double2(0.0, 0.0);
+      cplx acc2 = make_double2(0.0, 0.0);
+      if (live) {
+        const cplx* __restrict__ x = rho + row;  // column `row`: x_c = x[c * D]
+        if (wave == 0) {  // the diagonal element and the dense diagonal terms, in the application's order
+          xr = x[row * D];
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (k < A.n_diag) dsum = cfma(tc[A.diag_idx[k]], A.diag_val[k][row], dsum);
+          for (int k = 4; k < A.n_diag; ++k) {
+            const int t = A.diag_terms[k];
+            dsum = cfma(tc[t], A.terms[t].val[row], dsum);
+          }
+        }
+        const unsigned long long digits = gen_pack_digits(row, A.d, A.n_dig);
+        gen_fused_row<4, true>(A.F, wave, mv, mvd, dl, x, row, digits, mask, acc, dsum, D);
+        // the off-diagonal entries of row `row` again, this wave's sites in the same order, on y_c instead of x_c
+        for (int g = 0; g < A.F.n_groups; ++g) {
+          const int K = A.F.gK[g], s1 = A.F.gEnd[g];
+          for (int si_ = A.F.gBegin[g] + wave; si_ < s1; si_ += 4) {
+            const GenSiteF si = sites[si_];
+            const int R = (int)((digits >> si.shift0) & mask) * si.mul + (int)((digits >> si.shift1) & (unsigned)si.mask1);
+            const int e0 = si.ent_off + R * K;
+            for (int k = 0; k < K; ++k) {
+              const cplx m = mv[e0 + k];
+              if (m.x == 0.0 && m.y == 0.0) continue;  // (padding, or a drive that is off at this time)
+              acc2 = cfma(m, gen_dm_col_entry(A, tc, mv, mvd, dl, x, row + dl[e0 + k], mask, D), acc2);
+            }
+          }
+        }
+      }
+      if (wave != 0) {
+        cplx* r = red + ((wave - 1) * GEN_FUSED_ROWS + lane) * 3;
+        r[0] = acc;
+        r[1] = dsum;
+        r[2] = acc2;
+      }
+      __syncthreads();
+      if (wave == 0 && live) {
+#pragma unroll
+        for (int w = 0; w < 3; ++w) {
+          const cplx* r = red + (w * GEN_FUSED_ROWS + lane) * 3;
+          const cplx a = r[0], dd = r[1], a2 = r[2];
+          acc.x += a.x; acc.y += a.y;
+          dsum.x += dd.x; dsum.y += dd.y;
+          acc2.x += a2.x; acc2.y += a2.y;
+        }
+        acc = cfma(dsum, xr, acc);     // y_r = (G rho)_rr
+        acc2 = cfma(dsum, acc, acc2);  // (G G rho)_rr
+        e1 -= acc.y;
+        e2 -= acc2.x;
+        tr += xr.x;
+      }
+      __syncthreads();  // wave 0 has read the partial sums: the next row block may write them
+    }
+    if (wave == 0) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        e1 += __shfl_down(e1, o, 64);
+        e2 += __shfl_down(e2, o, 64);
+        tr += __shfl_down(tr, o, 64);
+      }
+      if (lane == 0) {
+        double* o = A.out + (size_t)s * A.out_stride;
+        atomicAdd(o + A.off, e1);
+        atomicAdd(o + A.off + 1, e2);
+        if (A.with_norm) atomicAdd(o + A.norm_off, tr);
+      }
+    }
+    // (every wave has passed the last row block's second barrier after its last read of `mv`: it may be staged again)
   }
 }
 

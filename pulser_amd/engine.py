@@ -1048,13 +1048,42 @@ class GeneralEngine:
                                                      self._stream()))
         return _obs_unpack(out, n)
 
+    def observe_density_many(self, states: Any, times: Any, one: int = 0, occupation: bool = True,
+                             correlation: bool = True, energy: bool = True) -> dict[str, np.ndarray]:
+        """``ryd_general_observe_density_many``: what :meth:`observe` with ``density=True`` returns, for the density
+        matrices of every evaluation time of a master-equation run in one device call and one device-to-host copy.
+        ``states`` is a complex128 tensor ``[T, B, dim, dim]`` on this engine's device, or any view of one whose last
+        two axes are contiguous: the strides of the first two axes are passed on, so ``dev[:, b:b + 1]`` of a snapshot
+        tensor is observed in place.  ``times`` [T] (us) need not be sorted or distinct; ``B`` is anything.  Ket engines
+        only (H(t) is this engine's); the energy moments need :meth:`apply_path` ``fused`` / ``fused_lds`` and an engine
+        without collapse operators.  The matrices are read as stored (not assumed Hermitian), the real part is kept.
+        Returns host arrays ``norm2`` [T, B] (the trace), ``occupation`` [T, B, N], ``correlation`` [T, B, N, N],
+        ``energy`` [T, B], ``energy2`` [T, B] - NOT normalised (divide by ``norm2``); what was not asked for is 0."""
+        torch = self.torch
+        one = int(one)
+        if not 0 <= one < self.local_dim:
+            raise ValueError(f"'one' must be a digit in [0, {self.local_dim}), got {one}")
+        if not 2 <= self.local_dim <= 4:
+            raise ValueError(f"observe_density_many takes local dimensions 2 - 4, got {self.local_dim}")
+        if self.is_density:
+            raise ValueError("observe_density_many is for ket engines; a density engine observes vec(rho) with observe")
+        n_t, n_b, stride_t, stride_b, tt = _many_args(torch, self.device, states, times, (self.dim, self.dim))
+        n = self.n
+        what = _obs_what(occupation, correlation, energy)
+        out = torch.empty((n_t, n_b, n * n + n + 3), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.ryd_general_observe_density_many(self._h, states.data_ptr(), n_t, n_b, stride_t, stride_b,
+                                                             tt.ctypes.data, what, self.local_dim, n, one,
+                                                             out.data_ptr(), self._stream()))
+        return _obs_unpack(out, n)
+
     def set_path(self, force_multi_launch: bool, no_sites: bool = False, no_fused: bool = False,
                  observe_small_chunks: bool = False) -> None:
         """Test hook: one launch per Taylor stage instead of the persistent
         one-launch kernel used for vectors of at most 4096 entries; ``no_sites``: the term-by-term
         kernel instead of the site-fused application of matrix-free terms; ``no_fused``: the round-3 site kernel
         (k_gen_apply_sites) instead of the padded site tables of k_gen_apply_fused; ``observe_small_chunks``:
-        :meth:`observe` of density matrices takes 5 columns per chunk (the chunked path on a small state)."""
+        :meth:`observe` of density matrices takes 5 columns per chunk (the chunked path on a small state),
+        :meth:`observe_many` and :meth:`observe_density_many` 5 evaluation times per chunk of tables."""
         _lib.check(self.lib.ryd_set_path(self._h, int(bool(force_multi_launch)) | (4096 if no_sites else 0)
                                          | (262144 if no_fused else 0) | (524288 if observe_small_chunks else 0)))
 

@@ -1140,7 +1140,9 @@ class QutipEmulator:
         kw = self._engine_kwargs(options, general=True)
         # ``general_device_snapshots`` (sesolve kets): the solved tensor stays in HBM behind a SnapshotStore, one per
         # trajectory, and the results hold LazyState objects - what the 2-level path always does
-        keep = bool(options.get("general_device_snapshots")) and mode == "sesolve"
+        # ``general_density_snapshots`` (mesolve matrices): the same, every snapshot viewed as a [D, D] matrix
+        keep_dm = bool(options.get("general_density_snapshots")) and mode == "mesolve"
+        keep = (bool(options.get("general_device_snapshots")) and mode == "sesolve") or keep_dm
         solved: list[tuple[np.ndarray, Any]] = []
         engines = [GeneralEngine(lower_general(prob, mesolve=(mode == "mesolve"))) for prob in problems]
         try:
@@ -1148,7 +1150,8 @@ class QutipEmulator:
                 # every trajectory's snapshot tensor is on the device at once (the stores are built after the last
                 # solve), next to each engine's work vectors: the budget counts the kets of ALL trajectories per time
                 self._check_snapshot_budget(len(times) - 1, 16 * sum(eng.dim for eng in engines),
-                                            "evaluation time (the kets of all trajectories)")
+                                            "evaluation time (the density matrices of all trajectories)" if keep_dm
+                                            else "evaluation time (the kets of all trajectories)")
             states = [eng.new_state(np.asarray(self._initial_state).reshape(-1)) for eng in engines]
             firsts = [st.cpu().numpy()[0] for st in states]
             if len(engines) > 1 and all(eng.dim <= 4096 for eng in engines) and np.all(np.diff(times) > 0):
@@ -1166,12 +1169,17 @@ class QutipEmulator:
                 eng.close()
         for prob, (first, host) in zip(problems, solved):
             D = len(prob["eigenbasis"]) ** n
+            if keep_dm:  # [T - 1, 1, D * D] as solved: a view, nothing moves
+                host = host.reshape(host.shape[0], 1, D, D)
             store = SnapshotStore(host) if keep else None
             results = []
             for i, t in enumerate(times):
                 st: Any
                 if keep:
-                    st = QState(first) if i == 0 else LazyState(store, i - 1, 0, (D, 1))
+                    if i == 0:
+                        st = QState(first.reshape(D, D) if keep_dm else first)
+                    else:
+                        st = LazyState(store, i - 1, 0, (D, D) if keep_dm else (D, 1))
                 else:
                     st = first if i == 0 else host[i - 1][0]
                     if mode == "mesolve":
@@ -1283,6 +1291,13 @@ class QutipEmulator:
         ``general_device_snapshots=True``: the kets of a multi-level / XY run without collapse operators stay on the
         GPU (one ``SnapshotStore`` per trajectory) and ``results.states`` holds ``LazyState`` objects that cross PCIe
         when they are read, as the states of a 2-level run do; by default they are host ``QState`` objects.
+
+        ``general_density_snapshots=True``: the same for the density matrices of a multi-level / XY master-equation run
+        (collapse operators, ``eff_noise``): the solved ``[T - 1, 1, D, D]`` tensor of every trajectory stays on the GPU
+        behind its own ``SnapshotStore`` (16 D^2 bytes per trajectory and evaluation time, checked against the snapshot
+        budget for all trajectories together before the solve) and the results hold ``LazyState`` matrices; the
+        initial state stays a host ``QState``.  A run without collapse operators ignores it, as a master-equation run
+        ignores ``general_device_snapshots``.
 
         ``mc_ensemble=True``: the deterministic-noise quantum-jump run on the tuned 2-level jump kernels
         (``Solver.MCSOLVER`` / ``n_trajectories`` on one Hamiltonian) keeps d^N numbers per trajectory to the end: the
