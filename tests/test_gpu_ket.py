@@ -123,7 +123,10 @@ def _single_atom_lindblad(omega, delta, gamma, t):
 @pytest.mark.parametrize("n, gamma", [(10, 0.5), (14, 0.05)])
 def test_split_operator_rows_product_state_full_size(n, gamma):
     """Non-interacting atoms under a constant drive: rho(t) is the product of single-atom
-    Lindblad solutions - an exact reference at any size (14 atoms: rho = 4.29 GB)."""
+    Lindblad solutions - an exact reference at any size (14 atoms: rho = 4.29 GB).  Its limits: the atoms are identical
+    under one constant drive, so a factor on the wrong bit or a drive read from the wrong atom leaves the reference
+    unchanged, and 60 um is non-interacting only over these 8 ns (5e-6 after 40 ns, tests/test_lindblad_ref.py); registers
+    without two like atoms and with interaction are pinned by tests/test_gpu_lindblad_edges.py."""
     import torch
 
     coords = P.register_coords(P.square_rect(1, n), 60.0)  # U ~ 1e-4 rad/us: negligible
@@ -312,7 +315,10 @@ def test_split_operator_rows_with_double_flip_dissipators(case, n):
 
 
 def test_split_operator_rows_relaxation_product_state_12_atoms():
-    """Non-interacting atoms with relaxation + dephasing: exact product of single-atom solutions."""
+    """Non-interacting atoms with relaxation + dephasing: exact product of single-atom solutions.  Its limits: identical
+    atoms under one constant drive (a bit or atom mix-up leaves the reference unchanged) and a 60-um spacing that is
+    non-interacting only over these 8 ns; tests/test_gpu_lindblad_edges.py pins the same path on interacting registers
+    without two like atoms."""
     import torch
     from scipy.linalg import expm
 
