@@ -337,7 +337,9 @@ def test_large_ket_against_the_product_state_solution():
     """25 atoms (0.5 GiB ket, three tiled passes per application, 64-bit index
     arithmetic): with the atoms far apart every atom evolves on its own, so any
     amplitude is a product of single-atom amplitudes.  (tools/big_ket.py runs the
-    same check at 28 and 30 atoms = 4 and 16 GiB kets.)"""
+    same check at 28 and 30 atoms = 4 and 16 GiB kets.)  Identical atoms: blind to any
+    permutation of the atom bits - tests/test_gpu_ket_clusters.py compares every amplitude
+    of registers in which no two atoms are alike."""
     from pulser_amd import problem as P
 
     n, T = 25, 8

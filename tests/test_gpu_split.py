@@ -181,7 +181,9 @@ def test_split_14_atoms_single_sequence_is_default_and_matches_ket_kernel():
 
 def test_split_large_ket_against_the_product_state_solution():
     """25 atoms (0.5 GiB ket, three tilings: 64-bit index arithmetic, strided tiles) on the default
-    path: with the atoms far apart every amplitude is a product of single-atom amplitudes."""
+    path: with the atoms far apart every amplitude is a product of single-atom amplitudes.  (Identical atoms: blind to any
+    permutation of the atom bits - tests/test_gpu_ket_clusters.py compares every amplitude of registers in which no two atoms
+    are alike.)"""
     n, T = 25, 8
     coords = P.register_coords(P.square_rect(1, n), 40.0)
     samples = {"amp": np.full(T + 1, 6.0), "det": np.full(T + 1, -2.0), "phase": np.zeros(T + 1)}
@@ -313,7 +315,8 @@ def test_large_tiles_give_21_to_23_atoms_one_pass_per_stage(n):
     """2^13-amplitude tiles (k_split_s<13>; 21 - 22 atoms): two tilings instead of three, so a stage is ONE pass over
     the ket; identical amplitudes to the 2^12 tiles (the same arithmetic in another order of the tile bits), and
     the exact product-state solution of far-apart atoms.  23 atoms stay on 2^12 tiles (two passes per stage: measured
-    faster than the runtime-indexed kernel a 10 + 3 bit tiling would need)."""
+    faster than the runtime-indexed kernel a 10 + 3 bit tiling would need).  (Identical atoms: blind to any permutation of the
+    atom bits - tests/test_gpu_ket_clusters.py runs both tile sizes on registers in which no two atoms are alike.)"""
     T = 6
     coords = P.register_coords(P.square_rect(1, n), 40.0)
     rng = np.random.default_rng(n)
