@@ -225,7 +225,7 @@ static int launch_split_reg(ryd_handle* h, const SplitArgs& A, const SplitRun& R
     const bool nr4 = nr_env != 5;
     if (nr4 && !n_rows && !h->mc && split_real(h)) {
       constexpr int NT4 = 256;
-      const size_t lds4 = (size_t)2 * NT4 * 4 * 16 + SPLITR_TRIG * 16 + (size_t)(NT4 / 64) * 16 * 16 +
+      const size_t lds4 = (size_t)2 * NT4 * 4 * 16 + SPLITR_TRIG * 16 + (size_t)(NT4 / 64) * splitr_gtab_slots<12, 4>(false, false, false, false) * 16 +
                           (SPLIT_MAX_SUB * SPLIT_MAX_STAGES + 2) * 8 + (SPLITR_EMODE ? 4 * NT4 * 8 : 0) + (128 + 32) * 8;
       const long long stride4 = (long long)h->B * N * 4;
       if (snap)
@@ -238,6 +238,9 @@ static int launch_split_reg(ryd_handle* h, const SplitArgs& A, const SplitRun& R
   }
   const size_t lds = (size_t)2 * NT * 8 * 16 + SPLITR_TRIG * 16 + (size_t)(NT / 64) * 32 * 16 +
                      (SPLIT_MAX_SUB * SPLIT_MAX_STAGES + 2) * 8 + (SPLITR_EMODE ? 4 * NT * 8 : 0) + (128 + 32) * 8;
+  // the plain real-drive kernel: four copies of the G table where lane bits 4, 5 ride on the pass (SPLITR_XPASS: <14, 5> only;
+  // every other instantiation launched below keeps the request it had - <13, 5>: two workgroups per CU)
+  const size_t lds_x = lds + (size_t)(NT / 64) * (splitr_gtab_slots<N, 5>(false, false, false, false) - 32) * 16;
   const int dev = h->cfg.device;
   static bool attr[64] = {};
   if (dev < 0 || dev >= 64 || !attr[dev]) {
@@ -274,7 +277,7 @@ static int launch_split_reg(ryd_handle* h, const SplitArgs& A, const SplitRun& R
     if constexpr (N == 14)
       hipLaunchKernelGGL((k_split_reg<14, 6, false>), dim3(1, h->B), dim3(256), lds, st, A, R, stride);
   } else
-    hipLaunchKernelGGL((k_split_reg<N, 5, false>), dim3(1, h->B), dim3(NT), lds, st, A, R, stride);
+    hipLaunchKernelGGL((k_split_reg<N, 5, false>), dim3(1, h->B), dim3(NT), lds_x, st, A, R, stride);
   HIPCHK(hipGetLastError());
   return RYD_OK;
 }

@@ -96,11 +96,29 @@
 #ifndef SPLITR_LATE
 #define SPLITR_LATE 1
 #endif
-//   SPLITR_P5 1 (round-6 variant, NTB == 2 shapes with TMODE 1): lane bit 5 changes places with T bit 1 INSIDE the LDS pass - the
-//                reader fetches from lane (l & 31) | (t1 << 5) - instead of by 64 v_permlane32_swap per stage; the pass then moves
-//                HALF the ket at a time (T bit 0 fixed: two super-chunks through the one 128-KiB buffer, 4 barriers as before)
-#ifndef SPLITR_P5
-#define SPLITR_P5 0
+//   SPLITR_XPASS 1 (default; the plain real-drive kernels with two T bits and wave bits, <14, 5> and <12, 4>, and the SNAP twin
+//                of <12, 4> - splitr_xpass() below; profiles/xpass.md): lane bits 4, 5 change places with the two T bits INSIDE the LDS pass instead of by
+//                128 v_permlane16/32_swap per stage.  Convention: the register NAMED with T bits (s0, s1) holds, on a lane with bits
+//                (l4, l5), the amplitude whose T-position index bits are (s0 ^ l4, s1 ^ l5).  The exchange is then: reader lane l
+//                fills its registers named (s0, s1) from the registers of the same name of lane l ^ (s0 << 4 | s1 << 5) - a constant
+//                per chunk, chunk (0, 0) reads its own lane, the four chunks, the two buffers and the 4 barriers stay, and every
+//                16-lane group of a ds_read_b128 still covers 256 consecutive bytes.  The convention reproduces itself: writer lane
+//                bit a' = s ^ a holds (T position P = a', lane position Q = a); the reader with l5 = a gets lane-position bit Q = a
+//                and T bit P = s ^ a, named s again.  What follows from it:
+//                  * addresses (load, store, snapshot, check epilogue) are "lane word XOR register constant": SplitRegLayout::index_x;
+//                  * tan-form rotations use one formula on both partners, so a rotation of a T bit does not care which name is which;
+//                    the two atoms that arrive from lane bits 4, 5 are rotated AFTER the pass, as soon as their pairs of chunks are in;
+//                  * phase factors stay decomposed in ACTUAL excitation bits: on a lane whose T bit j is flipped the product tree
+//                    runs over named bits with F'_j = 1 / F_j and B' = B F_j - done on the arguments: ev'_j = -ev_j, et' = et +
+//                    sum of the flipped ev_j (per-lane constants of the prologue), the sign of Dr[j] by an integer XOR, and in the
+//                    lane's detuning sum the terms of lane bits 4, 5 select between two scalars (l5 ? Dr[T1] : Dl[5]: the T-position
+//                    atom and its lane-position partner contribute under complementary conditions - one select, one addition);
+//                  * G(r) is uniform in actual bits: a lane reads G[r ^ c], c = l4 << NW | l5 << (NW + 1); every wave writes its table
+//                    four times, permuted (copy c holds G[r ^ c] at slot r, copies one slot apart in the banks: a 16-lane read group
+//                    meets two copies), and the 2^NR reads stay reads at offsets 16 k on one address register.
+//                0: the swaps (A/B)
+#ifndef SPLITR_XPASS
+#define SPLITR_XPASS 1
 #endif
 #ifndef SPLITR_LATE_REAL
 #define SPLITR_LATE_REAL 0  /* the same for real drives (A/B) */
@@ -114,7 +132,7 @@
 //                   split_ychain.hpp), and comes home after the last rotation: 12 moves per amplitude instead of 16 with four
 //                   DPP bits.  The chain runs hop by hop over a chunk, and the stores of the previous chunk are spread over
 //                   its steps (write_pre below) - that, not the moves, is most of what was measured;
-//                2: the way home rides on the LDS pass instead (NW > 0, not SPLITR_P5): pass_write stores x to the lane's own
+//                2: the way home rides on the LDS pass instead (NW > 0): pass_write stores x to the lane's own
 //                   slot and y to the slot of the lane it belongs to (same wave, same 8-lane group, before the same barrier):
 //                   10 moves per amplitude, but two 8-byte stores per amplitude, 2-way bank conflicts each (measured: not
 //                   faster than 1 beyond the noise)
@@ -149,11 +167,57 @@ struct SplitRegLayout {
     for (int j = 0; j < NR; ++j) i |= ((r >> j) & 1u) << regbit(odd, j);
     return i;
   }
+  // SPLITR_XPASS: the same map where a T register bit named s holds the T-position bit s ^ (the lane's bit ND + m): the lane's
+  // word carries its upper lane bits a second time, on the T positions, and the register's bits are XORed onto it
+  __host__ __device__ static constexpr unsigned index_x(bool odd, unsigned t, unsigned r) {
+    unsigned i = index(odd, t, r);
+    for (int m = 0; m < NTB; ++m) i ^= ((t >> (ND + m)) & 1u) << regbit(odd, NW + m);
+    return i;
+  }
+  // ... as the kernel computes it: the lane's word lw = index_x(odd, t, 0) XOR the named T bits, plus the other register bits
+  // (constants per register; SplitXAddrCheck below sweeps every lane and register of both parities at compile time)
+  __host__ __device__ static constexpr unsigned addr_x(bool odd, unsigned lw, unsigned r) {
+    constexpr unsigned tmask = ((1u << NTB) - 1u) << NW;
+    return (lw ^ index(odd, 0u, r & tmask)) + index(odd, 0u, r & ~tmask);
+  }
   // swizzle of the intra-wave transposition: slot of (low lane bits a, X, run Y) = a + 2^ND (X ^ (Y & FM)); chosen so
   // that the 16-lane groups of a ds_read_b128 and the 8-lane groups of a ds_write_b128 meet 16 different bank quads
   // (tools/lane_layout_check.py replays the bank rules of the guide for every instantiated shape)
   static constexpr int FM = ND == 4 ? 0 : (ND == 3 ? 2 : 3);
   __host__ __device__ static constexpr int swz(int y) { return ND == 3 ? ((y >> 1) & 1) : (y & FM); }
+};
+
+// SPLITR_XPASS: the instantiations whose lane bits 4, 5 change places with the T bits inside the pass, and the slots of 16 bytes
+// their G tables take per wave (four copies, NA + 1 slots apart) - the kernel's carve-up of the LDS and the host's request
+// (host_split.hpp: launch_split_reg) both come from here
+// (SNAP at 32 amplitudes per lane keeps the swaps: with the snapshot store in the loop the kernel sits at 256 vector registers
+// without scratch only with them; at 16 amplitudes per lane the snapshot twin takes the exchange like the plain kernel)
+template <int N, int NR>
+__host__ __device__ constexpr bool splitr_xpass(bool decay, bool rows, bool cplx, bool snap) {
+  return SPLITR_XPASS != 0 && SPLITR_TMODE == 1 && SplitRegLayout<N, NR>::NTB == 2 && SplitRegLayout<N, NR>::NW > 0 && !decay && !rows &&
+         !cplx && !(snap && NR >= 5) && !SPLITR_GMODE && !(SPLITR_KO & 4);
+}
+template <int N, int NR>
+__host__ __device__ constexpr int splitr_gtab_slots(bool decay, bool rows, bool cplx, bool snap) {
+  return splitr_xpass<N, NR>(decay, rows, cplx, snap) ? 4 * ((1 << NR) + 1) : (1 << NR);
+}
+
+template <int N, int NR>
+constexpr bool splitr_xaddr_ok(bool odd, unsigned r) {  // addr_x against index_x on every lane, register r
+  typedef SplitRegLayout<N, NR> L;
+  for (unsigned t = 0; t < (64u << L::NW); ++t)
+    if (L::addr_x(odd, L::index_x(odd, t, 0u), r) != L::index_x(odd, t, r) || L::index_x(odd, t, r) >= (1u << N)) return false;
+  return true;
+}
+template <int N, int NR, int R>
+struct SplitXAddrCheck {  // (one assertion per register: each stays inside the compiler's budget of constant-expression steps)
+  static_assert(splitr_xaddr_ok<N, NR>(false, R) && splitr_xaddr_ok<N, NR>(true, R),
+                "SPLITR_XPASS: lane word XOR named T bits + the other register bits must be index_x, even and odd layout");
+  static constexpr bool ok = SplitXAddrCheck<N, NR, R - 1>::ok;
+};
+template <int N, int NR>
+struct SplitXAddrCheck<N, NR, -1> {
+  static constexpr bool ok = true;
 };
 
 // compile-time loop: every register index below is a constant expression (runtime-trip loops with `continue` filters
@@ -239,11 +303,18 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
   constexpr int NG = 1 << NW;          // groups of the transposition (pass bits fixed)
   constexpr int GR = 1 << NTB;         // registers per group
   constexpr int NBUF = CH / GR;        // groups that fit a wave's private slice of buffer 0 (1 or 2)
+  // SPLITR_XPASS: the kernels whose lane bits 4, 5 change places with the T bits inside the pass (the layout is private to a launch)
+  constexpr bool kX = splitr_xpass<N, NR>(DECAY, ROWS, CPLX, SNAP);
+  static_assert(!kX || (CH == (1 << NW) && (NR == 4 || NR == 5)), "SPLITR_XPASS: a chunk = one named T pair, 1 or 2 lanes per G value");
+  constexpr int GC = kX ? 4 : 1;       // copies of a wave's G table (copy c holds G[r ^ (c << NW)] at slot r)
+  constexpr int GS = kX ? NA + 1 : NA; // slots from copy to copy: the two copies a 16-lane read group meets lie 4 banks apart
+  if constexpr (kX) static_assert(SplitXAddrCheck<N, NR, NA - 1>::ok, "SPLITR_XPASS: the address form of the loads and stores");
+  static_assert(GC * GS == splitr_gtab_slots<N, NR>(DECAY, ROWS, CPLX, SNAP), "the host sizes the G tables by splitr_gtab_slots");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   cplx* pbuf = reinterpret_cast<cplx*>(smem);  // 2 buffers x (NT * CH) slots of 16 B
   cplx* trig = pbuf + 2 * NT * CH;             // SPLITR_TRIG
-  cplx* gtab = trig + SPLITR_TRIG;             // [waves][NA]: G(r) of the current stage, wave-private
-  double* wtab = reinterpret_cast<double*>(gtab + (NT / 64) * NA);  // [SPLIT_MAX_SUB * SPLIT_MAX_STAGES + 1] (WMODE 1)
+  cplx* gtab = trig + SPLITR_TRIG;             // [waves][GC][GS]: G(r) of the current stage, wave-private
+  double* wtab = reinterpret_cast<double*>(gtab + (NT / 64) * GC * GS);  // [SPLIT_MAX_SUB * SPLIT_MAX_STAGES + 1] (WMODE 1)
   double* etab = wtab + (SPLIT_MAX_SUB * SPLIT_MAX_STAGES + 2);     // [4][NT]: et, eg of the even / odd layout (EMODE 1)
 
   const unsigned t = threadIdx.x;
@@ -279,6 +350,17 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
 #pragma unroll
     for (int j = 0; j < NR; ++j) ev[o][j] = e0[L::index(o, tq, (NA - 1) ^ (1u << j))] - et[o];
     eg[o] = e0[L::index(o, NT - 1, l & (NA - 1))];
+    if constexpr (kX) {
+      // (SPLITR_XPASS) the pieces above are in ACTUAL bits; on a lane whose T bit m is flipped the tree runs over the named bit:
+      // F' = 1 / F, B' = B F.  No pair term of the two T atoms here: G carries it (the lane reads G[r ^ c]).
+#pragma unroll
+      for (int m = 0; m < NTB; ++m) {
+        if ((l >> (ND + m)) & 1u) {
+          et[o] += ev[o][NW + m];
+          ev[o][NW + m] = -ev[o][NW + m];
+        }
+      }
+    }
     if (SPLITR_EMODE) {
       etab[(2 * o) * NT + t] = et[o];
       etab[(2 * o + 1) * NT + t] = eg[o];
@@ -338,9 +420,13 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
   double xr[NA], xi[NA];
   {
     const double fl = (ROWS && A.use_pre) ? row_factor(0, L::index(false, tq, 0u), L::index(false, NT - 1, 0u)) : 1.0;
+    // (SPLITR_XPASS: address = the lane's word XOR the named T bits, plus the pass bits)
+    const unsigned lw0 = kX ? L::index_x(false, tq, 0u) : 0u;
     splitr_for<0, NA>([&](auto Rc) {
       constexpr int r = decltype(Rc)::value;
-      const cplx v = st[L::index(false, tq, r)];
+      cplx v;
+      if constexpr (kX) v = st[L::addr_x(false, lw0, r)];
+      else v = st[L::index(false, tq, r)];
       const double f = (ROWS && A.use_pre) ? fl * ftl[128 + r] : 1.0;
       xr[r] = v.x * f;
       xi[r] = v.y * (ROWS ? f * csgn : f);
@@ -468,7 +554,8 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
     cplx Gq[GR];
     auto g_fetch = [&](auto Gc) {
       constexpr int g = decltype(Gc)::value;
-      const cplx* __restrict__ gq = gtab + w * NA;
+      // (SPLITR_XPASS: the copy of the lane's (l4, l5) - G[r ^ c] at slot r)
+      const cplx* __restrict__ gq = kX ? gtab + w * (GC * GS) + ((l >> ND) & 3u) * GS : gtab + w * NA;
       splitr_for<0, GR>([&](auto Ic) {
         constexpr int rho = GR - 1 - decltype(Ic)::value;  // (the order phase_group uses them in)
         Gq[rho] = gq[g | (rho << NW)];
@@ -477,13 +564,33 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
     if (!(SPLITR_KO & 8)) {
       double dthr = 0.0;
 #pragma unroll
-      for (int j = 0; j < 6; ++j) dthr += ((tq >> j) & 1u) ? 0.0 : Dl[j];
+      for (int j = 0; j < 6; ++j) {
+        // (SPLITR_XPASS: a lane with bit ND + m set holds the atom of T bit m flipped - that atom's integral joins B's argument
+        // exactly where the lane's own does not: one select, one addition)
+        if (kX && j >= ND) dthr += ((tq >> j) & 1u) ? Dr[NW + (j >= ND ? j - ND : 0)] : Dl[j];
+        else dthr += ((tq >> j) & 1u) ? 0.0 : Dl[j];
+      }
 #pragma unroll
       for (int j = 0; j < NW; ++j) dthr += ((tq >> (6 + j)) & 1u) ? 0.0 : Dw[j];
       double sc = cprod;
       if (DECAY)  // H_eff: the real factor exp(wE (dec_a + dec_b popc(index))): lane part here, register part in F
         sc *= exp(wE * (A.dec_a + A.dec_b * (double)(__popc(tq) + NR)));
       const double dF = DECAY ? exp(-wE * A.dec_b) : 1.0;  // an excited register atom: one set bit fewer
+      // the detuning integral of register bit j in F_j's argument (SPLITR_XPASS: minus it where the lane holds T bit j flipped)
+      auto drs = [&](int j) -> double {
+        if (kX && j >= NW) return __hiloint2double(__double2hiint(Dr[j]) ^ (int)(((l >> (ND + (j >= NW ? j - NW : 0))) & 1u) << 31), __double2loint(Dr[j]));
+        return Dr[j];
+      };
+      // the G table of the wave (SPLITR_XPASS: four permuted copies, lane l & (NA - 1) of each replica writes its share of them)
+      auto g_store = [&]() {
+        if constexpr (kX) {
+          constexpr int RB = 6 - NR;  // 2^RB lanes hold the same G value
+          splitr_for<0, (4 >> RB)>([&](auto Ic) {
+            const unsigned cpy = RB == 2 ? (l >> 4) : ((unsigned)decltype(Ic)::value | ((l >> 5) << 1));
+            gtab[w * (GC * GS) + cpy * GS + ((l & (NA - 1)) ^ (cpy << NW))] = Gl;
+          });
+        }
+      };
       if constexpr (kGAhead) {
         // the same seven expmi on the same arguments; only the order of issue differs: table reads, G's series, the G
         // table and the first group's reads of it, then the other six series (which cover those reads)
@@ -492,10 +599,11 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
         const cplx tB = expmi_arg(fma(wE, et_s, -dthr), rB);
         cplx tF[NR];
 #pragma unroll
-        for (int j = 0; j < NR; ++j) tF[j] = expmi_arg(fma(wE, odd ? ev[1][j] : ev[0][j], -Dr[j]), rF[j]);
+        for (int j = 0; j < NR; ++j) tF[j] = expmi_arg(fma(wE, odd ? ev[1][j] : ev[0][j], -drs(j)), rF[j]);
         __builtin_amdgcn_sched_barrier(0);
         Gl = expmi_fin(rG, tG);
-        gtab[w * NA + (l & (NA - 1))] = Gl;
+        if constexpr (kX) g_store();
+        else gtab[w * NA + (l & (NA - 1))] = Gl;
         __builtin_amdgcn_wave_barrier();
         g_fetch(splitr_c<NG - 1>{});
         __builtin_amdgcn_sched_barrier(0);
@@ -511,12 +619,13 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
       Bf = make_double2(Bf.x * sc, Bf.y * sc);
 #pragma unroll
       for (int j = 0; j < NR; ++j) {
-        F[j] = expmi(fma(wE, odd ? ev[1][j] : ev[0][j], -Dr[j]));
+        F[j] = expmi(fma(wE, odd ? ev[1][j] : ev[0][j], -drs(j)));
         if (DECAY) F[j] = make_double2(F[j].x * dF, F[j].y * dF);
       }
       Gl = expmi(wE * eg_s);
       if (!SPLITR_GMODE) {
-        gtab[w * NA + (l & (NA - 1))] = Gl;
+        if constexpr (kX) g_store();
+        else gtab[w * NA + (l & (NA - 1))] = Gl;
         __builtin_amdgcn_wave_barrier();
       }
       }
@@ -527,7 +636,7 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
       load_rot((cptr_t)cl);
     }
     cprod = cnext;
-    const cplx* __restrict__ gw = gtab + w * NA;
+    const cplx* __restrict__ gw = kX ? gtab + w * (GC * GS) + ((l >> ND) & 3u) * GS : gtab + w * NA;
     auto gval = [&](auto Rc) -> cplx {  // G(r): uniform
       constexpr int r = decltype(Rc)::value;
       if (SPLITR_GMODE) {
@@ -574,7 +683,6 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
         __builtin_amdgcn_sched_barrier(0);
       }
     };
-    constexpr bool kP5 = SPLITR_P5 && SPLITR_TMODE == 1 && NTB == 2 && NW > 0 && !(SPLITR_KO & 4);
     auto swap_d = [](double& a, double& c, auto is32) {
       unsigned alo = (unsigned)__double2loint(a), ahi = (unsigned)__double2hiint(a);
       unsigned clo = (unsigned)__double2loint(c), chi = (unsigned)__double2hiint(c);
@@ -592,17 +700,15 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
     };
     // SPLITR_YCHAIN: the shapes and builds that take the y chain, and whether its last hop rides on the pass
     constexpr bool kYChain = SPLITR_YCHAIN != 0 && !CPLX && SPLITR_HM == 1 && SPLITR_TMODE == 1 && !SPLITR_B2 && !(SPLITR_KO & 2) && ND >= 2;
-    constexpr bool kYStore = kYChain && SPLITR_YCHAIN == 2 && NW > 0 && !kP5 && !(SPLITR_KO & 4);
+    constexpr bool kYStore = kYChain && SPLITR_YCHAIN == 2 && NW > 0 && !(SPLITR_KO & 4);
     auto t_swap = [&](auto Gc) {  // SPLITR_TMODE 1 (NTB == 2): T bit 0 <-> lane bit 4, T bit 1 <-> lane bit 5
       constexpr int g = decltype(Gc)::value;
       if (SPLITR_KO & 1) return;
       constexpr int r0 = g, r1 = g | (1 << NW), r2 = g | (2 << NW), r3 = g | (3 << NW);
       swap_d(xr[r0], xr[r1], std::false_type{}); swap_d(xi[r0], xi[r1], std::false_type{});
       swap_d(xr[r2], xr[r3], std::false_type{}); swap_d(xi[r2], xi[r3], std::false_type{});
-      if constexpr (!kP5) {  // (SPLITR_P5: lane bit 5 <-> T bit 1 rides on the LDS pass)
-        swap_d(xr[r0], xr[r2], std::true_type{}); swap_d(xi[r0], xi[r2], std::true_type{});
-        swap_d(xr[r1], xr[r3], std::true_type{}); swap_d(xi[r1], xi[r3], std::true_type{});
-      }
+      swap_d(xr[r0], xr[r2], std::true_type{}); swap_d(xi[r0], xi[r2], std::true_type{});
+      swap_d(xr[r1], xr[r3], std::true_type{}); swap_d(xi[r1], xi[r3], std::true_type{});
     };
     auto t_write = [&](auto Gc) {
       constexpr int g = decltype(Gc)::value;
@@ -632,7 +738,7 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
       });
     };
     auto rot_t_new = [&](auto Gc) {  // the upper lane bits, now in the T registers
-      splitr_for<0, (kP5 ? 1 : NTB)>([&](auto Mc) {  // (SPLITR_P5: lane bit 5 arrives with the pass; its rotation follows the read)
+      splitr_for<0, NTB>([&](auto Mc) {
         constexpr int m = decltype(Mc)::value;
         rot_reg(splitr_c<NW + m>{}, Tl[ND + m], Ul[ND + m], splitr_c<PW>{}, Gc);
       });
@@ -731,7 +837,7 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
     // (Shapes whose groups go through the LDS transposition issue them behind the group loop.)  The address is the scalar
     // c4 plus the stride; the touched values pass through an empty asm so that their use cannot be pulled forward.
     unsigned wv[8];
-    constexpr bool kWarmLate = (SPLITR_KWARM == 2 || SPLITR_KWARM == 3) && !kP5 && NW > 0 && !(SPLITR_KO & 4);
+    constexpr bool kWarmLate = (SPLITR_KWARM == 2 || SPLITR_KWARM == 3) && NW > 0 && !(SPLITR_KO & 4);
     // (complex drives issue them behind the loop too: <14, 5, DECAY, CPLX> spills a vector register otherwise)
     constexpr bool kWarmInLoop = kWarmLate && SPLITR_TMODE == 1 && NTB == 2 && !CPLX;
     auto warm_issue = [&]() {
@@ -779,6 +885,8 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
         rot_t_old(splitr_c<g>{});
         if constexpr (SPLITR_TMODE == 3) {
           // nothing to exchange
+        } else if constexpr (kX) {
+          // (SPLITR_XPASS) lane bits 4, 5 arrive with the pass; their rotations follow its reads (rot_x below)
         } else if constexpr (SPLITR_TMODE == 1 && NTB == 2) {
           t_swap(splitr_c<g>{});
           rot_t_new(splitr_c<g>{});
@@ -876,7 +984,8 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
     };
     auto pass_read = [&](auto Cc) {
       constexpr int c = decltype(Cc)::value;
-      const cplx* __restrict__ pb = pbuf + (c & 1) * (NT * CH) + l + 64 * NG * w;
+      // (SPLITR_XPASS: the chunk named (s0, s1) comes from the registers of the same name of lane l ^ (s0 << 4 | s1 << 5))
+      const cplx* __restrict__ pb = pbuf + (c & 1) * (NT * CH) + (kX ? l ^ (unsigned)(c << ND) : l) + 64 * NG * w;
       splitr_for<0, CH>([&](auto Kc) {
         constexpr int k = decltype(Kc)::value, kp = k & PW, ks = k >> NW;
         const cplx v = pb[64 * (kp + NG * NG * ks)];
@@ -885,60 +994,12 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
       });
     };
     typedef splitr_c<0> C0; typedef splitr_c<1> C1; typedef splitr_c<2> C2; typedef splitr_c<3> C3;
-    // SPLITR_P5: super-chunk S = the registers with T bit 0 (register bit NR - 2) = S, i.e. chunks S and S + 2;
-    // slot = lane + 64 (A + NG (B + NG t1)): writer A = wave, B = pass bits, t1 = its T bit 1, lane = its own;
-    //                                         reader A = its pass bits, B = its wave, t1 = ITS LANE BIT 5, lane = (l & 31) | (t1' << 5)
-    auto pass_write5 = [&](auto Sc) {
-      constexpr int S = decltype(Sc)::value;
-      cplx* __restrict__ pb = pbuf + t;
-      splitr_for<0, 2 * CH>([&](auto Kc) {
-        constexpr int k = decltype(Kc)::value, kp = k & PW, t1 = k >> NW;
-        constexpr int r = kp | (S << (NR - 2)) | (t1 << (NR - 1));
-        pb[64 * NG * (kp + NG * t1)] = make_double2(xr[r], xi[r]);
-      });
+    // SPLITR_XPASS: the atom that arrived on T bit M from lane bit ND + M, on the pairs of chunks whose other T bit is V
+    auto rot_x = [&](auto Mc, auto Vc) {
+      constexpr int m = decltype(Mc)::value, v = decltype(Vc)::value;
+      rot_reg(splitr_c<NW + m>{}, Tl[ND + m], Ul[ND + m], splitr_c<(1 << (NW + 1 - m))>{}, splitr_c<(v << (NW + 1 - m))>{});
     };
-    auto pass_read5 = [&](auto Sc) {
-      constexpr int S = decltype(Sc)::value;
-      const cplx* __restrict__ pb = pbuf + (l & 31u) + 64 * NG * (w + NG * (l >> 5));
-      splitr_for<0, 2 * CH>([&](auto Kc) {
-        constexpr int k = decltype(Kc)::value, kp = k & PW, t1 = k >> NW;
-        constexpr int r = kp | (S << (NR - 2)) | (t1 << (NR - 1));
-        const cplx v = pb[32 * t1 + 64 * kp];
-        xr[r] = v.x;
-        xi[r] = v.y;
-      });
-    };
-    auto pre5 = [&](auto Sc) {
-      constexpr int S = decltype(Sc)::value;
-      pre(splitr_c<S>{}); pre(splitr_c<S + 2>{});
-    };
-    auto post5 = [&](auto Sc) {  // the wave bits (register bits 0 .. NW-1) and lane bit 5's atom (T bit 1) of the half that arrived
-      constexpr int S = decltype(Sc)::value;
-      post(splitr_c<S>{}); post(splitr_c<S + 2>{});
-      rot_reg(splitr_c<NW + 1>{}, Tl[ND + 1], Ul[ND + 1], splitr_c<(1 << (NR - 2))>{}, splitr_c<(S << (NR - 2))>{});
-    };
-    if constexpr (kP5) {
-      static_assert(CH == (1 << NW), "SPLITR_P5: chunks of 2^NW registers");
-      pre5(C0{});
-      __syncthreads();  // the previous stage's pass_read5(1) of every wave is done: the buffer may be overwritten
-      pass_write5(C0{});
-      pre5(C1{});
-      __syncthreads();
-      pass_read5(C0{});
-      if (SPLITR_KWARM) {
-        typedef const __attribute__((address_space(4))) unsigned* uptr_t;
-        uptr_t nx = (uptr_t)(unsigned long long)(coefs + (size_t)(sg + 1 < n_stages ? sg + 1 : sg) * stage_stride);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) warm ^= nx[k < 7 ? 16 * k : 8 * N - 1];
-      }
-      __syncthreads();
-      pass_write5(C1{});
-      post5(C0{});
-      __syncthreads();
-      pass_read5(C1{});
-      if (SPLITR_PREF) load_next(sg + 1 < n_stages ? sg + 1 : sg, !odd);
-      post5(C1{});
-    } else if constexpr (NW == 0 || (SPLITR_KO & 4)) {
+    if constexpr (NW == 0 || (SPLITR_KO & 4)) {
       pre(C0{}); pre(C1{}); pre(C2{}); pre(C3{});
       post(C0{}); post(C1{}); post(C2{}); post(C3{});
     } else {
@@ -972,11 +1033,24 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
       pass_write(C3{});
       post(C0{});
       post(C1{});
+      // (SPLITR_XPASS) the arriving atoms.  A rotation restricted to some chunks commutes with another one only if both are
+      // whole on the registers they share: T bit 0 on the pair (C0, C1) once both have their wave bits; T bit 1 mixes C0 with
+      // C2 and C1 with C3, so it waits until T bit 0 is done on all four - after pass_read(C3).  That tail overlaps the next
+      // stage's table-and-series work, which does not depend on it.
+      if constexpr (kX) {
+        post(C2{});
+        rot_x(C0{}, C0{});
+      }
       __syncthreads();
       pass_read(C3{});
       if (SPLITR_PREF) load_next(sg + 1 < n_stages ? sg + 1 : sg, !odd);
-      post(C2{});
+      if constexpr (!kX) post(C2{});
       post(C3{});
+      if constexpr (kX) {
+        rot_x(C0{}, C1{});
+        rot_x(C1{}, C0{});
+        rot_x(C1{}, C1{});
+      }
     }
     odd = !odd;
     }
@@ -995,21 +1069,24 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
           // address = uniform base + the lane's word + a constant per register.  The lane's word is laundered through an
           // empty asm: loop-invariant otherwise, and the 32 hoisted 64-bit addresses cost 20 spilled vector registers
           // in every stage of the loop (measured: 10.6 instead of 9.4 us per stage)
-          unsigned lw = odd ? L::index(true, tq, 0u) : L::index(false, tq, 0u);
+          // (SPLITR_XPASS: the lane's word XOR the named T bits - four bases - plus the other register bits)
+          unsigned lw = kX ? (odd ? L::index_x(true, tq, 0u) : L::index_x(false, tq, 0u)) : (odd ? L::index(true, tq, 0u) : L::index(false, tq, 0u));
           asm volatile("" : "+v"(lw));
           cplx* __restrict__ sd = A.snap_map_slots > 0 ? A.snaps + ((size_t)moff << N)
                                              : A.snaps + (size_t)slot * A.snap_stride + ((size_t)b << N);
           if (odd) {
             splitr_for<0, NA>([&](auto Rc) {
               constexpr int r = decltype(Rc)::value;
-              __builtin_nontemporal_store(xr[r], &sd[lw + L::index(true, 0u, r)].x);
-              __builtin_nontemporal_store(xi[r], &sd[lw + L::index(true, 0u, r)].y);
+              const unsigned ix = kX ? L::addr_x(true, lw, r) : lw + L::index(true, 0u, r);
+              __builtin_nontemporal_store(xr[r], &sd[ix].x);
+              __builtin_nontemporal_store(xi[r], &sd[ix].y);
             });
           } else {
             splitr_for<0, NA>([&](auto Rc) {
               constexpr int r = decltype(Rc)::value;
-              __builtin_nontemporal_store(xr[r], &sd[lw + L::index(false, 0u, r)].x);
-              __builtin_nontemporal_store(xi[r], &sd[lw + L::index(false, 0u, r)].y);
+              const unsigned ix = kX ? L::addr_x(false, lw, r) : lw + L::index(false, 0u, r);
+              __builtin_nontemporal_store(xr[r], &sd[ix].x);
+              __builtin_nontemporal_store(xi[r], &sd[ix].y);
             });
           }
         }
@@ -1049,7 +1126,7 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
       cplx* __restrict__ out = A.dst ? A.dst + boff : st;
       cplx* __restrict__ out2 = A.dst2 ? A.dst2 + boff : nullptr;
       const cplx* __restrict__ ref = A.cmp ? A.cmp + boff : nullptr;
-      const unsigned lw = odd ? L::index(true, tq, 0u) : L::index(false, tq, 0u);
+      const unsigned lw = kX ? (odd ? L::index_x(true, tq, 0u) : L::index_x(false, tq, 0u)) : (odd ? L::index(true, tq, 0u) : L::index(false, tq, 0u));
       double dmax = 0.0, dsum = 0.0;
       auto put = [&](unsigned ix, double vx, double vy) {
         const cplx v = make_double2(vx, vy);
@@ -1063,10 +1140,11 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
           dsum += d2;
         }
       };
+      // (SPLITR_XPASS: the named T bits are XORed onto the lane's word, the other register bits added)
       if (odd) {
-        splitr_for<0, NA>([&](auto Rc) { constexpr int r = decltype(Rc)::value; put(lw + L::index(true, 0u, r), xr[r], xi[r]); });
+        splitr_for<0, NA>([&](auto Rc) { constexpr int r = decltype(Rc)::value; put(kX ? L::addr_x(true, lw, r) : lw + L::index(true, 0u, r), xr[r], xi[r]); });
       } else {
-        splitr_for<0, NA>([&](auto Rc) { constexpr int r = decltype(Rc)::value; put(lw + L::index(false, 0u, r), xr[r], xi[r]); });
+        splitr_for<0, NA>([&](auto Rc) { constexpr int r = decltype(Rc)::value; put(kX ? L::addr_x(false, lw, r) : lw + L::index(false, 0u, r), xr[r], xi[r]); });
       }
       if (ref) {
         for (int o = 32; o > 0; o >>= 1) {
@@ -1090,7 +1168,8 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
   splitr_for<0, NA>([&](auto Rc) {
     constexpr int r = decltype(Rc)::value;
     const double f = (ROWS && A.use_post) ? fl * ftl[128 + r] : 1.0;
-    st[odd ? L::index(true, tq, r) : L::index(false, tq, r)] = make_double2(xr[r] * f, xi[r] * (ROWS ? f * csgn : f));
+    const unsigned ix = kX ? (odd ? L::index_x(true, tq, r) : L::index_x(false, tq, r)) : (odd ? L::index(true, tq, r) : L::index(false, tq, r));
+    st[ix] = make_double2(xr[r] * f, xi[r] * (ROWS ? f * csgn : f));
   });
   }
   }  // rows

@@ -1,6 +1,7 @@
 """Replays the LDS bank rules for the stores and loads of k_split_reg (pulser_amd/csrc/k_split_reg.hpp), per shape:
 the intra-wave transposition (swizzled slots), the pass between the waves (16-byte slots, one per lane) and the split
 8-byte stores of SPLITR_YCHAIN 2 (x to the lane's own slot, y to the slot of lane t ^ shift).  No GPU, no compiler.
+For the shapes of SPLITR_XPASS also the permuted reads of the pass and the four copies of the G table.
 
 Bank rules (CDNA4 LDS, 64 banks of 4 bytes; a wave64 access is served in fixed lane groups, one LDS cycle per group
 when conflict-free, one more per extra distinct address on a busy bank):
@@ -63,6 +64,17 @@ def check_shape(n, nr):
     out.append((f"pass_write, y of SPLITR_YCHAIN 2 (slot t ^ {s})", "ds_write_b64", [16 * (l ^ s) + 8 for l in range(64)], False))
     # every slot is written exactly once by the pair of split stores: x half by its lane, y half by lane ^ shift
     assert sorted([16 * l for l in range(64)] + [16 * (l ^ s) + 8 for l in range(64)]) == [8 * k for k in range(128)]
+    if ntb == 2 and nw > 0 and nr in (4, 5):  # SPLITR_XPASS: lane bits 4, 5 change places with the T bits inside the pass
+        for c in range(1, 4):  # pass_read of the chunk named (s0, s1): the slot of lane l ^ (s0 << 4 | s1 << 5)
+            out.append((f"pass_read, SPLITR_XPASS chunk {c} (slot l ^ {c << 4})", "ds_read_b128", [16 * (l ^ (c << 4)) for l in range(64)], True))
+        na, gs = 1 << nr, (1 << nr) + 1  # four copies of the G table, NA + 1 slots apart; copy c holds G[r ^ (c << NW)] at slot r
+        for k in range(4 >> (6 - nr)):  # the stores: 64 / NA lanes hold the same G value and share the four copies
+            cpy = [(l >> 4) if nr == 4 else (k | ((l >> 5) << 1)) for l in range(64)]
+            out.append((f"G table store {k}, SPLITR_XPASS (4 copies)", "ds_write_b128",
+                        [16 * (cpy[l] * gs + ((l & (na - 1)) ^ (cpy[l] << nw))) for l in range(64)], True))
+        # a read of G(r): every lane the slot r of the copy of its (l4, l5) - two addresses per 16-lane group, 4 banks apart
+        out.append(("G table read, SPLITR_XPASS (copy of l4, l5)", "ds_read_b128", [16 * ((l >> 4) * gs) for l in range(64)], True))
+        out.append(("G table read, copies NA slots apart (not used)", "ds_read_b128", [16 * ((l >> 4) * na) for l in range(64)], False))
     if not (ntb == 2):  # the transposition through LDS (SPLITR_TMODE 1 swaps registers instead when NTB == 2)
         for rho in range(gr):  # t_write: slot = 64 NG run + la + ((lT ^ swz(rho)) << ND), run = rho
             addr = [16 * ((l & ((1 << nd) - 1)) + (((l >> nd) ^ swz(nd, rho)) << nd)) for l in range(64)]
