@@ -1690,19 +1690,30 @@ def _overlap_many_route(states: Sequence[Any], fires: Sequence[bool],
     return store, b, positions, len(tail) == 2
 
 
-def _mc_ensemble_route(sim: QutipEmulator, config: "QutipConfig") -> bool:
+def _mc_ensemble_route(sim: QutipEmulator, config: "QutipConfig", general_jumps: bool = False) -> bool:
     """Whether a run with ``QutipBackendV2.mc_ensemble = True`` takes ``QutipEmulator.run(mc_ensemble=True)``: the
     deterministic-noise quantum-jump run on the tuned two-level jump kernels, no callbacks, and nothing but observables
     that are linear in the averaged state's diagonal or served by the trajectory means (``BitStrings``, ``Occupation``,
     ``CorrelationMatrix``, ``Energy``, ``EnergySecondMoment``, ``EnergyVariance`` themselves, not subclasses).  Anything
-    else (``StateResult``, ``Fidelity``, ``Expectation``, a callback) reads the density matrix: today's route."""
+    else (``StateResult``, ``Fidelity``, ``Expectation``, a callback) reads the density matrix: today's route.
+
+    ``general_jumps`` (the backend's attribute of that name): a jump run the tuned kernels do not take - a multi-level
+    basis, XY mode, a non-diagonal ``sum C^dag C`` - qualifies too (``run(general_jumps=True, mc_ensemble=True)``),
+    when every ``Occupation`` / ``CorrelationMatrix`` names a one-state that is one of the eigenstates or can be
+    inferred from them."""
     if has_stochastic_noise(sim.noise_model) or config.callbacks:
         return False
     allowed = (BitStrings, Occupation, CorrelationMatrix, Energy, EnergySecondMoment, EnergyVariance)
     if not all(type(o) in allowed for o in config.observables):
         return False
     problem = sim._current_problem
-    return sim._solver_mode(problem) == "mcsolve" and sim._mc_fast_ok(problem)
+    if sim._solver_mode(problem) != "mcsolve":
+        return False
+    if sim._mc_fast_ok(problem):
+        return True
+    eigenstates = sim._hamiltonian_data.eigenbasis
+    return bool(general_jumps) and all(_one_digit(eigenstates, o.one_state) is not None for o in config.observables
+                                       if isinstance(o, (Occupation, CorrelationMatrix)))
 
 
 # ------------------------------------------------------------------- backend
@@ -1738,6 +1749,13 @@ class QutipBackendV2:
     # (QutipEmulator.run(mc_ensemble=True)): d^N numbers per trajectory, no 16-GiB cap on the evaluation times.  Values
     # agree with the default route's within rounding, not bit for bit; every other run is left exactly as it is.
     mc_ensemble: bool = False
+    # True: a run that takes qutip.mcsolve but not the tuned two-level jump kernels (3- / 4-level bases, XY mode,
+    # collapse operators whose sum C^dag C is not diagonal) runs as quantum-jump trajectories on the general path
+    # (QutipEmulator.run(general_jumps=True)): kets of d^N amplitudes instead of the master-equation fallback and its
+    # 2^26-entry Liouvillian cap.  Together with mc_ensemble the deterministic-noise run of such a register is reported
+    # from its kets too (_mc_ensemble_route): one device reduction per one-state the observables count, no [D, D]
+    # averages.  Set on an instance, like mc_ensemble; not a QutipConfig key.  False: no code path differs.
+    general_jumps: bool = False
     # True: the density matrices of a multi-level / XY master-equation run (3-level "all" basis, leakage, XY mode, any
     # eff_noise) stay on the device (QutipEmulator.run(general_density_snapshots=True)) and their occupations,
     # correlations and energy moments come from ONE GeneralEngine.observe_density_many call per distinct one-state, from
@@ -1799,7 +1817,7 @@ class QutipBackendV2:
     def run(self) -> Results:
         return self._run_raw(self._sim_obj, self._config, dict(self._options),
                              observe_many_min_times=self.observe_many_min_times, mc_ensemble=self.mc_ensemble,
-                             general_density_one_call=self.general_density_one_call)
+                             general_density_one_call=self.general_density_one_call, general_jumps=self.general_jumps)
 
     @staticmethod
     def run_from_sequence_samples(sequence_samples: Any, register: Any = None, device: Any = None,
@@ -1815,12 +1833,13 @@ class QutipBackendV2:
     @staticmethod
     def _run_raw(sim: QutipEmulator, config: QutipConfig, options: dict[str, Any], *,
                  observe_many_min_times: Any = "class", mc_ensemble: bool = False,
-                 general_density_one_call: bool = False) -> Results:
+                 general_density_one_call: bool = False, general_jumps: bool = False) -> Results:
         """``observe_many_min_times``: the threshold of the one-call observable path for this run (``run`` passes the
         instance's, so a subclass or an instance may set its own); by default the class attribute.  ``mc_ensemble``:
         the instance's ``QutipBackendV2.mc_ensemble``; it takes effect where ``_mc_ensemble_route`` allows.
         ``general_density_one_call``: the instance's attribute of that name; it takes effect on a multi-level / XY
-        master-equation run with enough firing evaluation times."""
+        master-equation run with enough firing evaluation times.  ``general_jumps``: the instance's attribute of that
+        name, handed to ``QutipEmulator.run`` as its option."""
         from .engine import Engine, GeneralEngine
         from .general import lower_general
         from .terms import SUPPORTED_BASES
@@ -1929,10 +1948,27 @@ class QutipBackendV2:
                 # (the energy moments need the padded site tables, as on the ket route)
                 general_one_call = general_one_call or (wants_energy and bool(watching))
         overlap_cache: dict[str, Any] = {}  # like many_cache, for overlapped_many
-        if mc_ensemble and _mc_ensemble_route(sim, config):
-            # the energy moments of the trajectories are those of the H(t) every HamiltonianOperator below wraps (the
-            # engine is built before the solve here: a two-level run without stochastic noise draws nothing for it)
-            options = {**options, "mc_ensemble": True, "mc_ensemble_observer": noiseless_engine()}
+        if general_jumps:
+            options = {**options, "general_jumps": True}
+        if mc_ensemble and _mc_ensemble_route(sim, config, general_jumps):
+            if sim._mc_fast_ok(sim._current_problem):
+                # the energy moments of the trajectories are those of the H(t) every HamiltonianOperator below wraps (the
+                # engine is built before the solve here: a two-level run without stochastic noise draws nothing for it)
+                options = {**options, "mc_ensemble": True, "mc_ensemble_observer": noiseless_engine()}
+            elif hdata.basis_name not in SUPPORTED_BASES or len(hdata.eigenbasis) != 2 or hdata.interaction_type == "XY":
+                # the general route on a multi-level / XY register: one reduction per distinct one-state (with none to
+                # count - energies only - the inferred one rides along, as in observed_many), by the engine below,
+                # lowered matrix-free for the energy moments (built before the solve: no stochastic noise, no draws)
+                found = {_one_digit(eigenstates, o.one_state) for o in watching if isinstance(o, (Occupation, CorrelationMatrix))}
+                general_one_call = True
+                options = {**options, "mc_ensemble": True,
+                           "mc_ensemble_digits": sorted(found) or [_one_digit(eigenstates, None) or 0],
+                           "mc_ensemble_observer": noiseless_engine()}
+            else:
+                # ... on a two-level Ising register (a non-diagonal sum C^dag C): every HamiltonianOperator below wraps
+                # a tuned Engine, which counts local state 0 and lets the observables complement; the solve builds its
+                # own general observer
+                options = {**options, "mc_ensemble": True, "mc_ensemble_digits": [0]}
 
         def overlapped_many(rs: Sequence[Any]) -> dict[int, tuple[dict[Any, np.ndarray], int, int]]:
             """position in ``rs`` -> (finished values [row, column] by observable, its row, its column), {} on the
@@ -2066,7 +2102,12 @@ class QutipBackendV2:
                 ham = HamiltonianOperator(noiseless_engine(), t * T / 1000, eigenstates, energy_expected=wants_energy)
                 if isinstance(r.state, EnsembleState):
                     e = r.state
-                    ham.seed(state, e.norm2, e.occupation, e.correlation, e.energy, e.energy2)
+                    if e.by_digit is None:
+                        ham.seed(state, e.norm2, e.occupation, e.correlation, e.energy, e.energy2)
+                    else:  # (the general route: one seed per digit counted, the energies with the first)
+                        for k, (d, v) in enumerate(e.by_digit.items()):
+                            ham.seed(state, e.norm2, v["occupation"], v["correlation"],
+                                     *((e.energy, e.energy2) if k == 0 else ()), digit=d)
                 if served is not None:
                     by_digit, row, b = served
                     for k, (d, got) in enumerate(by_digit.items()):

@@ -171,17 +171,34 @@ class EnsembleState(DeviceState):
     ``occupation`` [N] and ``correlation`` [N, N] count local state 0 (the first eigenstate), as ``Engine.observe``
     does; ``energy`` / ``energy2`` are the moments of the noiseless H(t); ``norm2`` is the mean squared norm of the
     kets (~ 1).  None of them is divided by ``norm2``.  ``occupation_stderr`` [N] is the sample standard deviation of
-    the per-trajectory occupations over sqrt(n_trajectories): the Monte-Carlo error of ``occupation``."""
+    the per-trajectory occupations over sqrt(n_trajectories): the Monte-Carlo error of ``occupation``.
+
+    ``by_digit`` (multi-level and XY registers, ``run(general_jumps=True, mc_ensemble=True)``): ``{digit:
+    {"occupation", "correlation", "occupation_stderr"}}`` for every local state counted, in the order asked for.
+    ``occupation``, ``correlation`` and ``occupation_stderr`` are then those of the first digit and need not be given;
+    without it ``by_digit`` is None and the object is that of the two-level route."""
 
     _REFUSAL = ("the trajectory-averaged density matrix was never formed (mc_ensemble=True keeps its diagonal and "
                 "the means of the built-in observables): run with mc_ensemble=False for {}")
 
-    def __init__(self, diag_sum: np.ndarray, n_trajectories: int, *, occupation: np.ndarray,
-                 correlation: np.ndarray, energy: float, energy2: float, norm2: float,
-                 occupation_stderr: np.ndarray) -> None:
+    def __init__(self, diag_sum: np.ndarray, n_trajectories: int, *, occupation: np.ndarray | None = None,
+                 correlation: np.ndarray | None = None, energy: float, energy2: float, norm2: float,
+                 occupation_stderr: np.ndarray | None = None,
+                 by_digit: "dict[int, dict[str, np.ndarray]] | None" = None) -> None:
         d = np.asarray(diag_sum, dtype=np.float64).reshape(-1)
         if n_trajectories < 1:
             raise ValueError(f"n_trajectories must be at least 1, got {n_trajectories}")
+        self.by_digit: dict[int, dict[str, np.ndarray]] | None = None
+        if by_digit is not None:
+            if not by_digit:
+                raise ValueError("by_digit needs at least one digit")
+            keys = ("occupation", "correlation", "occupation_stderr")
+            self.by_digit = {int(k): {name: np.asarray(v[name], dtype=np.float64) for name in keys}
+                             for k, v in by_digit.items()}
+            first = next(iter(self.by_digit.values()))
+            occupation, correlation, occupation_stderr = (first[name] for name in keys)
+        elif occupation is None or correlation is None or occupation_stderr is None:
+            raise TypeError("occupation, correlation and occupation_stderr are needed without by_digit")
         self._tensor = None
         self._ket = None
         self.n_trajectories = int(n_trajectories)

@@ -230,6 +230,57 @@ def _as_inputs(sampled_seq: Any, register: Any, device: Any) -> SequenceInputs:
     raise TypeError("The provided sequence has to be a valid SequenceSamples instance.")
 
 
+class _EnsembleSums:
+    """The running sums over the trajectories of an ensemble route (``run(mc_ensemble=True)``): what ``observe_many``
+    returns per trajectory - ``[T', B, ...]`` host arrays, not normalised - summed over the trajectory axis per local
+    state counted (``digits``; the two-level kernels count local state 0), with the squared occupations for the
+    standard error; :meth:`states` turns them into one ``EnsembleState`` per evaluation time."""
+
+    def __init__(self, n_times: int, n_qudits: int, digits: Any = (0,)) -> None:
+        self.digits = tuple(digits)
+        self._n_times = int(n_times)
+        self._sums: dict[int, dict[str, np.ndarray]] = {d: {} for d in self.digits}
+        self._occ_sq = {d: np.zeros((self._n_times, n_qudits)) for d in self.digits}
+
+    def add(self, rows: dict[str, np.ndarray], at: slice, weight: int = 1, digit: int | None = None) -> None:
+        """Add the rows of the evaluation times ``at``, each trajectory ``weight`` times (``digit``: the first one)."""
+        digit = self.digits[0] if digit is None else digit
+        sums = self._sums[digit]
+        for k, v in rows.items():
+            if k not in sums:
+                sums[k] = np.zeros((self._n_times,) + tuple(v.shape[2:]))
+            sums[k][at] += weight * v.sum(axis=1)
+        self._occ_sq[digit][at] += weight * (rows["occupation"] ** 2).sum(axis=1)
+
+    def _means(self, digit: int, ntraj: int) -> dict[str, np.ndarray]:
+        """Trajectory means of the pair sums of ``digit`` [T, ...] and the standard error of its occupations."""
+        sums, occ_sq = self._sums[digit], self._occ_sq[digit]
+        mean_occ = sums["occupation"] / ntraj
+        with np.errstate(invalid="ignore", divide="ignore"):  # (one trajectory has no sample deviation: nan)
+            var = np.maximum(occ_sq - ntraj * mean_occ ** 2, 0.0) / (ntraj - 1) if ntraj > 1 else np.full_like(occ_sq, np.nan)
+            stderr = np.sqrt(var / ntraj)
+        if ntraj > 1:
+            stderr[0] = 0.0  # every trajectory starts in the same ket (not left to the rounding of sum x^2 - n mean^2)
+        return {"occupation": mean_occ, "correlation": sums["correlation"] / ntraj, "occupation_stderr": stderr}
+
+    def states(self, diag_sums: np.ndarray, ntraj: int, with_energy: bool = True,
+               by_digit: bool = False) -> list[EnsembleState]:
+        """One ``EnsembleState`` per evaluation time from the summed diagonals ``diag_sums`` [T, D]; the norm and the
+        energy moments are those that came with the first digit (``with_energy=False``: nan).  ``by_digit``: the
+        states carry the means of every digit, else those of the first one as plain attributes."""
+        means = {d: self._means(d, ntraj) for d in self.digits}
+        lead, first = self._sums[self.digits[0]], means[self.digits[0]]
+        out = []
+        for i in range(self._n_times):
+            pairs: dict[str, Any] = (
+                {"by_digit": {d: {k: v[i] for k, v in m.items()} for d, m in means.items()}} if by_digit
+                else {k: v[i] for k, v in first.items()})
+            out.append(EnsembleState(diag_sums[i], ntraj, norm2=lead["norm2"][i] / ntraj,
+                                     energy=lead["energy"][i] / ntraj if with_energy else math.nan,
+                                     energy2=lead["energy2"][i] / ntraj if with_energy else math.nan, **pairs))
+        return out
+
+
 class QutipEmulator:
     """Emulator of a pulse sequence on MI355X (drop-in for
     ``pulser_simulation.QutipEmulator``; arguments as simulation.py:130-141)."""
@@ -860,6 +911,8 @@ class QutipEmulator:
             mode = self._solver_mode(problems[0])
             if mode == "mcsolve" and not self._mc_fast_ok(problems[0]):
                 if options.get("general_jumps"):
+                    if mc_ntraj is not None and options.get("mc_ensemble"):
+                        return [self._solve_general_jumps_ensemble(problems[0], mc_ntraj, options)]
                     return self._solve_general_jumps(problems, options, mc_ntraj)
                 mode = "mesolve"
             if mode == "mcsolve":
@@ -1062,17 +1115,8 @@ class QutipEmulator:
             noiseless["collapse_ops"] = []
             observer = Engine.from_problems([noiseless], mode="sesolve")
         t_us = np.asarray(times, dtype=np.float64)
-        sums: dict[str, np.ndarray] = {}
-        occ_sq = np.zeros((len(times), n))
-
-        def add(rows: dict[str, np.ndarray], at: slice, weight: int = 1) -> None:
-            # rows: [T', B, ...] per trajectory, not normalised -> the sums over the trajectory axis
-            for k, v in rows.items():
-                if k not in sums:
-                    sums[k] = np.zeros((len(times),) + tuple(v.shape[2:]))
-                sums[k][at] += weight * v.sum(axis=1)
-            occ_sq[at] += weight * (rows["occupation"] ** 2).sum(axis=1)
-
+        sums = _EnsembleSums(len(times), n)
+        add = sums.add
         try:
             torch = observer.torch
             diag = torch.zeros((len(times), D), dtype=torch.float64, device=observer.device)
@@ -1102,27 +1146,105 @@ class QutipEmulator:
             if own_observer:
                 observer.close()
         self.last_mc_jumps = np.concatenate(jumps)
-        mean_occ = sums["occupation"] / ntraj
-        with np.errstate(invalid="ignore", divide="ignore"):  # (one trajectory has no sample deviation: nan)
-            var = np.maximum(occ_sq - ntraj * mean_occ ** 2, 0.0) / (ntraj - 1) if ntraj > 1 else np.full_like(occ_sq, np.nan)
-            stderr = np.sqrt(var / ntraj)
-        if ntraj > 1:
-            stderr[0] = 0.0  # every trajectory starts in the same ket (not left to the rounding of sum x^2 - n mean^2)
+        return self._ensemble_results(sums.states(host, ntraj))
+
+    def _ensemble_results(self, states: list[EnsembleState]) -> CoherentResults:
+        """The results of an ensemble route: one ``StateResult`` per evaluation time around its ``EnsembleState``."""
+        times = self._eval_times_array
         meas_errors = (
             {"epsilon": self.noise_model.p_false_pos, "epsilon_prime": self.noise_model.p_false_neg}
             if "SPAM" in self.noise_model.noise_types else None
         )
         qids = tuple(self.samples_obj.qubit_ids)
         results = [
-            StateResult(qids, self._meas_basis,
-                        EnsembleState(host[i], ntraj, occupation=mean_occ[i], correlation=sums["correlation"][i] / ntraj,
-                                      energy=sums["energy"][i] / ntraj, energy2=sums["energy2"][i] / ntraj,
-                                      norm2=sums["norm2"][i] / ntraj, occupation_stderr=stderr[i]),
-                        self._meas_basis in self.basis_name,
+            StateResult(qids, self._meas_basis, st, self._meas_basis in self.basis_name,
                         evaluation_time=float(t / (self._tot_duration * 1e-3)))
-            for i, t in enumerate(times)
+            for st, t in zip(states, times)
         ]
-        return CoherentResults(results, n, self.basis_name, times, self._meas_basis, meas_errors)
+        return CoherentResults(results, self._hamiltonian_data.n_qudits, self.basis_name, times, self._meas_basis,
+                               meas_errors)
+
+    def _solve_general_jumps_ensemble(self, problem: dict[str, Any], ntraj: int,
+                                      options: dict[str, Any]) -> CoherentResults:
+        """The deterministic run of :meth:`_solve_general_jumps` (``run(general_jumps=True, mc_ensemble=True)``) without
+        the averaged density matrices, as :meth:`_solve_mc_ensemble` is to :meth:`_solve_mc_average`: the same tables,
+        chunks, seeds and ``GeneralEngine.mc_solve`` calls integrate the same trajectories bit for bit; the diagonal
+        is reduced from the kets by ``ensemble_diag``, the occupations and correlations of every local state in
+        ``mc_ensemble_digits`` and the energy moments (with the first digit) by ``GeneralEngine.observe_many`` of a
+        noiseless batch-1 ket engine lowered matrix-free (``mc_ensemble_observer`` hands one in; it is left open).
+        The energy moments need the padded-table application of that engine (``apply_path()`` ``fused`` /
+        ``fused_lds``); a problem of more than 96 terms is lowered to CSR terms instead, and ``energy`` / ``energy2``
+        of its results are ``nan`` while the diagonal and the pair sums are served as usual."""
+        from .engine import GeneralEngine, ensemble_diag
+        from .general import lower_general
+        from .results import _ONE_STATE
+
+        times = self._eval_times_array
+        n = self._hamiltonian_data.n_qudits
+        eigenbasis = list(problem["eigenbasis"])
+        digits = options.get("mc_ensemble_digits")
+        if digits is None:
+            digits = [eigenbasis.index(_ONE_STATE[self._meas_basis])]
+        digits = list(dict.fromkeys(int(v) for v in digits))  # distinct, in the order asked for
+        if not digits or any(not 0 <= v < len(eigenbasis) for v in digits):
+            raise ValueError(f"mc_ensemble_digits must be local-state indices in [0, {len(eigenbasis)}) "
+                             f"({tuple(eigenbasis)}), got {digits}")
+        init = np.asarray(self._initial_state)
+        if init.ndim == 2 and init.shape[0] == init.shape[1] and init.shape[0] > 1:
+            raise NotImplementedError(
+                "Quantum-jump trajectories need a ket as initial state; use "
+                "solver=Solver.MESOLVER with a density matrix.")
+        ket = init.reshape(-1)
+        kw = self._engine_kwargs(options, general=True)
+        tables, cops = lower_general(problem, mesolve=False, with_collapse=True)
+        D = tables.dim
+        chunk = int(max(1, min(ntraj, 1024, (2 << 30) // max(1, D * 16 * len(times)))))
+        # per evaluation time: one row of the diagonals and the kets of one chunk (the solver's work copies are kets too)
+        self._check_snapshot_budget(len(times) - 1, D * 8 + chunk * D * 16,
+                                    "evaluation time (the ensemble diagonal and one chunk of kets)")
+        observer = options.get("mc_ensemble_observer")
+        own_observer = observer is None
+        if own_observer:
+            noiseless = dict(problem)
+            noiseless["collapse_ops"] = []
+            observer = GeneralEngine(lower_general(noiseless, mesolve=False, matrix_free=True))
+        t_us = np.asarray(times, dtype=np.float64)
+        sums = _EnsembleSums(len(times), n, digits)
+        try:
+            with_energy = observer.apply_path() in ("fused", "fused_lds")
+
+            def observe(kets: Any, t: np.ndarray, at: slice, weight: int = 1) -> None:
+                for k, digit in enumerate(digits):  # (only the first call carries the energy moments)
+                    sums.add(observer.observe_many(kets, t, one=digit, energy=with_energy and k == 0), at, weight, digit)
+
+            torch = observer.torch
+            diag = torch.zeros((len(times), D), dtype=torch.float64, device=observer.device)
+            first = observer.new_state(ket)[None]  # [1, 1, D]: every trajectory starts here
+            ensemble_diag(first, diag[:1])
+            diag[0] *= ntraj
+            observe(first, t_us[:1], slice(0, 1), ntraj)
+            del first
+            done = 0
+            jumps = []
+            while done < ntraj:
+                b = min(chunk, ntraj - done)
+                with GeneralEngine(tables, batch=b) as eng:
+                    eng.set_collapse(cops)
+                    state = eng.new_state(ket)
+                    snaps = eng.mc_solve(state, times, self._mc_seeds(b, options), **kw)
+                    ensemble_diag(snaps, diag[1:])
+                    observe(snaps, t_us[1:], slice(1, None))
+                    jumps.append(eng.mc_jumps())
+                    self.last_engine_stats = eng.stats()
+                    del state, snaps
+                done += b
+            host = diag.cpu().numpy()
+            del diag
+        finally:
+            if own_observer:
+                observer.close()
+        self.last_mc_jumps = np.concatenate(jumps)
+        return self._ensemble_results(sums.states(host, ntraj, with_energy=with_energy, by_digit=True))
 
     def _solve_general(self, problems: list[dict[str, Any]], mode: str,
                        options: dict[str, Any]) -> list[CoherentResults]:
@@ -1307,9 +1429,21 @@ class QutipEmulator:
         (sampling, ``sampling_dist``, the SPAM flips and ``expect`` of diagonal operators work unchanged) and the
         trajectory means ``occupation``, ``correlation``, ``energy``, ``energy2``, ``norm2`` with
         ``occupation_stderr``, equal to the values of the averaged matrix within rounding.  ``full()``, ``overlap``
-        and ``expect`` of other operators raise ``NotImplementedError``.  Every other run ignores the option.
+        and ``expect`` of other operators raise ``NotImplementedError``.  Every other run ignores the option
+        (but see ``general_jumps`` with it, below).
         ``mc_ensemble_observer``: a noiseless batch-1 sesolve ``Engine`` whose H(t) the energy moments use (left
-        open); by default one is built from the run's problem without its collapse operators."""
+        open); by default one is built from the run's problem without its collapse operators.
+
+        ``general_jumps=True`` with ``mc_ensemble=True``: the same for the deterministic-noise run of the general
+        path (multi-level bases, XY mode, a non-diagonal ``sum C^dag C``): the trajectories of ``general_jumps=True``
+        alone, bit for bit, reported as ``EnsembleState`` objects instead of ``[D, D]`` averages - 14 and more XY
+        atoms or 9 and more three-level atoms at any list of evaluation times.  ``mc_ensemble_digits``: the local
+        states (indices into the eigenbasis) whose occupations and correlations are kept, by default the one-state of
+        the measurement basis; ``EnsembleState.by_digit`` holds them all, ``occupation`` / ``correlation`` /
+        ``occupation_stderr`` those of the first.  An index outside ``[0, d)`` raises ``ValueError``.
+        ``mc_ensemble_observer`` is then a noiseless batch-1 ket ``GeneralEngine`` lowered matrix-free.  A problem of
+        more than 96 Hamiltonian terms has no padded-table application: ``energy`` and ``energy2`` of its results
+        are ``nan``, the diagonal and the pair sums are served as usual."""
         warnings.warn(
             "QutipEmulator is deprecated as of pulser 1.9. Please use QutipBackendV2 instead.",
             DeprecationWarning,
