@@ -124,10 +124,19 @@ class RydState:
     def to_qobj(self) -> QState:
         return self._state
 
+    # uuid of a Fidelity / Expectation -> the value computed for it on the device for this state (the deferred state of
+    # a device snapshot: ``engine.overlap_many`` / ``engine.expect_sparse`` over the store; the state around an
+    # ``EnsembleState``: its registered trajectory means): that observable's ``apply`` returns it
+    _seeded: dict[Any, Any] | None = None
+
+    def seed(self, observable: "Observable", value: Any) -> None:
+        if self._seeded is None:
+            self._seeded = {}
+        self._seeded[observable.uuid] = value
+
     def seeded_value(self, observable: "Observable") -> Any:
-        """A value already computed for ``observable`` on this state, or ``_UNSEEDED``: only the deferred state of a
-        device snapshot ever carries one."""
-        return _UNSEEDED
+        """A value already computed for ``observable`` on this state (``seed``), or ``_UNSEEDED``."""
+        return _UNSEEDED if self._seeded is None else self._seeded.get(observable.uuid, _UNSEEDED)
 
     def infer_one_state(self) -> str:
         """pulser/backend/state.py: the eigenstate measured as 1."""
@@ -279,9 +288,6 @@ class _DeferredRydState(RydState):
         self._amplitudes = None
         self._lazy = lazy
         self._q: QState | None = None
-        # uuid of a Fidelity / Expectation -> the value ``engine.overlap_many`` / ``engine.expect_sparse`` computed for
-        # this state on the device (``QutipBackendV2._overlap_many_route``): that observable's ``apply`` returns it
-        self._seeded: dict[Any, Any] = {}
 
     @property
     def _state(self) -> QState:  # type: ignore[override]
@@ -289,13 +295,6 @@ class _DeferredRydState(RydState):
             self._q = QState(np.asarray(self._lazy.unit()))
             self._lazy = None
         return self._q
-
-    def seed(self, observable: "Observable", value: Any) -> None:
-        self._seeded[observable.uuid] = value
-
-    def seeded_value(self, observable: "Observable") -> Any:
-        return self._seeded.get(observable.uuid, _UNSEEDED)
-
 
 class RydOperator:
     """``QutipOperator`` (pulser_simulation/qutip_op.py:30-260) on a SciPy sparse
@@ -1690,12 +1689,41 @@ def _overlap_many_route(states: Sequence[Any], fires: Sequence[bool],
     return store, b, positions, len(tail) == 2
 
 
-def _mc_ensemble_route(sim: QutipEmulator, config: "QutipConfig", general_jumps: bool = False) -> bool:
+def _overlap_form(obs: Any, eigenstates: Sequence[str], dim: int | None, density: bool) -> str | None:
+    """How the device serves ``obs`` on states of a run with ``eigenstates`` and dimension ``dim`` (None: any): "ket" /
+    "dm" (the kind of a Fidelity's target; "dm" only where the states are density matrices, ``density``), "op" (an
+    Expectation), or None where the per-time path has to answer - it rejects other eigenstates or sizes with its own
+    errors, and <psi|A|psi> with a dense A is not covered."""
+    if isinstance(obs, Fidelity):
+        target = obs.state
+        if target.eigenstates != tuple(eigenstates):
+            return None
+        q = target.to_qobj()
+        if not isinstance(q, QState) or dim not in (None, q.shape[0]):
+            return None
+        return "ket" if q.isket else ("dm" if density else None)
+    if isinstance(obs, Expectation):
+        op = obs.operator
+        if isinstance(op, RydOperator):
+            return "op" if op.eigenstates == tuple(eigenstates) and dim in (None, op.to_qobj().shape[0]) else None
+        return "op" if (op.ndim == 2 and op.shape[0] == op.shape[1] and dim in (None, op.shape[0])
+                        and op.dtype.kind in "biufc") else None
+    return None
+
+
+def _mc_ensemble_route(sim: QutipEmulator, config: "QutipConfig", general_jumps: bool = False,
+                       ket_observables: bool = False) -> bool:
     """Whether a run with ``QutipBackendV2.mc_ensemble = True`` takes ``QutipEmulator.run(mc_ensemble=True)``: the
     deterministic-noise quantum-jump run on the tuned two-level jump kernels, no callbacks, and nothing but observables
     that are linear in the averaged state's diagonal or served by the trajectory means (``BitStrings``, ``Occupation``,
     ``CorrelationMatrix``, ``Energy``, ``EnergySecondMoment``, ``EnergyVariance`` themselves, not subclasses).  Anything
     else (``StateResult``, ``Fidelity``, ``Expectation``, a callback) reads the density matrix: today's route.
+
+    ``ket_observables`` (the backend asks with it; without it the answer is the one above): a ``Fidelity`` whose
+    target ``_overlap_form`` classifies as "ket" - the run's eigenstates, a ket of the run's dimension - and an
+    ``Expectation`` it classifies as "op" qualify too, themselves and not subclasses: they are trajectory means of
+    per-ket numbers (``run(mc_ensemble_targets=..., mc_ensemble_operators=...)``).  A mixed-state target, other
+    eigenstates or another size keep today's route and its errors.
 
     ``general_jumps`` (the backend's attribute of that name): a jump run the tuned kernels do not take - a multi-level
     basis, XY mode, a non-diagonal ``sum C^dag C`` - qualifies too (``run(general_jumps=True, mc_ensemble=True)``),
@@ -1704,14 +1732,18 @@ def _mc_ensemble_route(sim: QutipEmulator, config: "QutipConfig", general_jumps:
     if has_stochastic_noise(sim.noise_model) or config.callbacks:
         return False
     allowed = (BitStrings, Occupation, CorrelationMatrix, Energy, EnergySecondMoment, EnergyVariance)
-    if not all(type(o) in allowed for o in config.observables):
+    eigenstates = sim._hamiltonian_data.eigenbasis
+    dim = len(eigenstates) ** sim._hamiltonian_data.n_qudits
+    from_kets = {Fidelity: "ket", Expectation: "op"} if ket_observables else {}
+    if not all(type(o) in allowed or (type(o) in from_kets
+                                      and _overlap_form(o, eigenstates, dim, False) == from_kets[type(o)])
+               for o in config.observables):
         return False
     problem = sim._current_problem
     if sim._solver_mode(problem) != "mcsolve":
         return False
     if sim._mc_fast_ok(problem):
         return True
-    eigenstates = sim._hamiltonian_data.eigenbasis
     return bool(general_jumps) and all(_one_digit(eigenstates, o.one_state) is not None for o in config.observables
                                        if isinstance(o, (Occupation, CorrelationMatrix)))
 
@@ -1746,7 +1778,9 @@ class QutipBackendV2:
     _OVERLAP_MANY_FLOOR = 128
     # True: a deterministic-noise quantum-jump run on the two-level jump kernels whose observables need nothing but the
     # diagonal and the trajectory means (_mc_ensemble_route) never forms the averaged density matrices
-    # (QutipEmulator.run(mc_ensemble=True)): d^N numbers per trajectory, no 16-GiB cap on the evaluation times.  Values
+    # (QutipEmulator.run(mc_ensemble=True)): d^N numbers per trajectory, no 16-GiB cap on the evaluation times.  A
+    # Fidelity with a ket target and an Expectation count among them: they are registered with the solve
+    # (mc_ensemble_targets / mc_ensemble_operators) and read back as trajectory means of per-ket numbers.  Values
     # agree with the default route's within rounding, not bit for bit; every other run is left exactly as it is.
     mc_ensemble: bool = False
     # True: a run that takes qutip.mcsolve but not the tuned two-level jump kernels (3- / 4-level bases, XY mode,
@@ -1908,24 +1942,7 @@ class QutipBackendV2:
             return dev[torch.as_tensor(idx, dtype=torch.long, device=dev.device)]
 
         def overlap_form(obs: Any, dim: int | None, density: bool) -> str | None:
-            """How the device serves ``obs`` on snapshots of dimension ``dim`` (None: any): "ket" / "dm" (the kind of a
-            Fidelity's target), "op" (an Expectation), or None where the per-time path has to answer - it rejects
-            other eigenstates or sizes with its own errors, and <psi|A|psi> with a dense A is not covered."""
-            if isinstance(obs, Fidelity):
-                target = obs.state
-                if target.eigenstates != tuple(eigenstates):
-                    return None
-                q = target.to_qobj()
-                if not isinstance(q, QState) or dim not in (None, q.shape[0]):
-                    return None
-                return "ket" if q.isket else ("dm" if density else None)
-            if isinstance(obs, Expectation):
-                op = obs.operator
-                if isinstance(op, RydOperator):
-                    return "op" if op.eigenstates == tuple(eigenstates) and dim in (None, op.to_qobj().shape[0]) else None
-                return "op" if (op.ndim == 2 and op.shape[0] == op.shape[1] and dim in (None, op.shape[0])
-                                and op.dtype.kind in "biufc") else None
-            return None
+            return _overlap_form(obs, eigenstates, dim, density)
 
         # the Fidelity / Expectation observables the device may serve (the dimension, and whether a density-matrix target
         # is served, show once the snapshots are there)
@@ -1950,7 +1967,19 @@ class QutipBackendV2:
         overlap_cache: dict[str, Any] = {}  # like many_cache, for overlapped_many
         if general_jumps:
             options = {**options, "general_jumps": True}
-        if mc_ensemble and _mc_ensemble_route(sim, config, general_jumps):
+        ensemble_seeds: list[tuple[Any, str, int]] = []  # (observable, EnsembleState attribute, position in it)
+        if mc_ensemble and _mc_ensemble_route(sim, config, general_jumps, ket_observables=True):
+            # a Fidelity with a ket target and an Expectation are trajectory means of per-ket numbers: registered with
+            # the solve, read back from every EnsembleState in fill
+            kets = [o for o in config.observables if type(o) is Fidelity]
+            ops = [o for o in config.observables if type(o) is Expectation]
+            if kets:
+                options = {**options, "mc_ensemble_targets": [np.asarray(o.state.to_qobj()).reshape(-1) for o in kets]}
+            if ops:
+                options = {**options, "mc_ensemble_operators": [
+                    o.operator.to_qobj() if isinstance(o.operator, RydOperator) else o.operator for o in ops]}
+            ensemble_seeds = ([(o, "fidelity", k) for k, o in enumerate(kets)]
+                              + [(o, "expectation", k) for k, o in enumerate(ops)])
             if sim._mc_fast_ok(sim._current_problem):
                 # the energy moments of the trajectories are those of the H(t) every HamiltonianOperator below wraps (the
                 # engine is built before the solve here: a two-level run without stochastic noise draws nothing for it)
@@ -2108,6 +2137,9 @@ class QutipBackendV2:
                         for k, (d, v) in enumerate(e.by_digit.items()):
                             ham.seed(state, e.norm2, v["occupation"], v["correlation"],
                                      *((e.energy, e.energy2) if k == 0 else ()), digit=d)
+                    for o, name, k in ensemble_seeds:  # (divided by the mean squared norm, as ham.seed divides)
+                        v = getattr(e, name)[k] / float(e.norm2)
+                        state.seed(o, float(v) if name == "fidelity" else complex(v))
                 if served is not None:
                     by_digit, row, b = served
                     for k, (d, got) in enumerate(by_digit.items()):

@@ -8,7 +8,7 @@ path happens in the hand-written HIP kernels of ``csrc/rydemu.hip`` through
 from __future__ import annotations
 
 import ctypes as C
-from typing import Any, Mapping, Sequence
+from typing import Any, Mapping, NamedTuple, Sequence
 
 import numpy as np
 
@@ -150,26 +150,23 @@ def accumulate(x: Any, acc: Any, weight: float = 1.0) -> None:
         torch.cuda.current_stream(x.device).cuda_stream))
 
 
-def expect_sparse(states: Any, operator: Any, *, density: bool = False) -> Any:
-    """``<x_s| O |x_s>`` for kets ``states`` complex128[S, D], or ``Tr(O rho_s)`` for density matrices
-    complex128[S, D, D] (``density=True``), on the device and for every state in one launch
-    (``ryd_expect_sparse``): ``qutip.expect`` of simresults.py:89-132 over the states of a run.  ``states`` is a
-    CUDA tensor whose inner dimensions are contiguous; dim 0 may be strided (``dev[:, b]`` of a ``[T, B, D]``
-    snapshot tensor).  ``operator`` is anything ``scipy.sparse`` accepts, D x D; only its stored non-zeros are
-    visited.  Returns a CUDA complex128 tensor [S]."""
+class SparseTriplets(NamedTuple):
+    """The stored non-zeros of a ``dim`` x ``dim`` operator as ``ryd_expect_sparse`` reads them, already on a device:
+    ``idx`` int32[2 nnz] (the rows, then the columns) and ``vals`` complex128[nnz], duplicates summed, sorted by
+    (row, column).  ``sparse_triplets`` builds one; ``expect_sparse`` takes it in place of the operator, so that a
+    caller with many stacks of states (the chunks of a trajectory ensemble) uploads the operator once."""
+
+    dim: int
+    nnz: int
+    idx: Any
+    vals: Any
+
+
+def _host_triplets(operator: Any, dim: int) -> tuple[np.ndarray, np.ndarray]:
+    """(rows then columns int32[2 nnz], values complex128[nnz]) of ``operator``'s stored non-zeros, checked against
+    ``dim``."""
     import scipy.sparse as sp
 
-    torch = _torch()
-    if not (hasattr(states, "is_cuda") and states.is_cuda):
-        raise ValueError("states must be a CUDA tensor")
-    if states.dtype != torch.complex128:
-        raise TypeError("complex128 tensor expected")
-    if states.dim() != (3 if density else 2) or (density and states.shape[1] != states.shape[2]):
-        raise ValueError(f"shape {tuple(states.shape)} does not match {'[S, D, D]' if density else '[S, D]'}")
-    n_states, dim = int(states.shape[0]), int(states.shape[-1])
-    inner = (dim, 1) if density else (1,)
-    if dim < 1 or (n_states > 0 and tuple(states.stride()[1:]) != inner) or (n_states > 1 and states.stride(0) < dim ** len(inner)):
-        raise ValueError("the inner dimensions of states must be contiguous (dim 0 may be strided)")
     m = sp.csr_matrix(operator) if not sp.issparse(operator) else operator.tocsr()
     if m.shape[0] != m.shape[1]:
         raise ValueError(f"square operator expected, got {tuple(m.shape)}")
@@ -185,11 +182,52 @@ def expect_sparse(states: Any, operator: Any, *, density: bool = False) -> Any:
     rows = np.repeat(np.arange(dim, dtype=np.int32), np.diff(m.indptr))
     if nnz and (len(rows) != nnz or cols.min() < 0 or cols.max() >= dim):
         raise ValueError("operator indices outside [0, dim)")
+    return np.concatenate([rows, cols]), np.ascontiguousarray(m.data, dtype=np.complex128)
+
+
+def sparse_triplets(operator: Any, dim: int, device: Any) -> SparseTriplets:
+    """``operator`` (anything ``scipy.sparse`` accepts, ``dim`` x ``dim``) as :class:`SparseTriplets` on ``device``."""
+    torch = _torch()
+    idx, vals = _host_triplets(operator, int(dim))
+    return SparseTriplets(int(dim), len(vals), torch.from_numpy(idx).to(device), torch.from_numpy(vals).to(device))
+
+
+def expect_sparse(states: Any, operator: Any, *, density: bool = False) -> Any:
+    """``<x_s| O |x_s>`` for kets ``states`` complex128[S, D], or ``Tr(O rho_s)`` for density matrices
+    complex128[S, D, D] (``density=True``), on the device and for every state in one launch
+    (``ryd_expect_sparse``): ``qutip.expect`` of simresults.py:89-132 over the states of a run.  ``states`` is a
+    CUDA tensor whose inner dimensions are contiguous; dim 0 may be strided (``dev[:, b]`` of a ``[T, B, D]``
+    snapshot tensor).  ``operator`` is anything ``scipy.sparse`` accepts, D x D; only its stored non-zeros are
+    visited - or the :class:`SparseTriplets` of one, uploaded earlier to the device of ``states``.  Returns a CUDA
+    complex128 tensor [S]."""
+    torch = _torch()
+    if not (hasattr(states, "is_cuda") and states.is_cuda):
+        raise ValueError("states must be a CUDA tensor")
+    if states.dtype != torch.complex128:
+        raise TypeError("complex128 tensor expected")
+    if states.dim() != (3 if density else 2) or (density and states.shape[1] != states.shape[2]):
+        raise ValueError(f"shape {tuple(states.shape)} does not match {'[S, D, D]' if density else '[S, D]'}")
+    n_states, dim = int(states.shape[0]), int(states.shape[-1])
+    inner = (dim, 1) if density else (1,)
+    if dim < 1 or (n_states > 0 and tuple(states.stride()[1:]) != inner) or (n_states > 1 and states.stride(0) < dim ** len(inner)):
+        raise ValueError("the inner dimensions of states must be contiguous (dim 0 may be strided)")
+    if isinstance(operator, SparseTriplets):
+        if operator.dim != dim:
+            raise ValueError(f"operator of shape {(operator.dim, operator.dim)} does not match states of dimension {dim}")
+        if operator.idx.device != states.device or operator.vals.device != states.device:
+            raise ValueError(f"operator triplets on {operator.idx.device}, states on {states.device}")
+        host = None
+    else:
+        host = _host_triplets(operator, dim)
     out = torch.empty(n_states, dtype=torch.complex128, device=states.device)
     if n_states == 0:
         return out
-    idx = torch.from_numpy(np.concatenate([rows, cols])).to(states.device)
-    vals = torch.from_numpy(np.ascontiguousarray(m.data, dtype=np.complex128)).to(states.device)
+    if host is None:
+        nnz, idx, vals = operator.nnz, operator.idx, operator.vals
+    else:
+        nnz = len(host[1])
+        idx = torch.from_numpy(host[0]).to(states.device)
+        vals = torch.from_numpy(host[1]).to(states.device)
     stride = int(states.stride(0)) if n_states > 1 else dim ** len(inner)
     _lib.check(_lib.load().ryd_expect_sparse(
         states.data_ptr(), n_states, stride, dim, int(bool(density)), idx.data_ptr(), idx.data_ptr() + 4 * nnz,

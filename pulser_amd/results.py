@@ -158,6 +158,21 @@ class DeviceState:
         return f"DeviceState(shape={self.shape}, {where})"
 
 
+def operator_key(m: Any) -> tuple:
+    """What identifies an operator (a dense array or a SciPy sparse matrix, as ``SimulationResults._as_operator``
+    returns it) among those registered for an ensemble run: its shape and its stored non-zeros - (shape, row pointers,
+    columns, values) of the complex128 CSR form, duplicates summed, stored zeros dropped, sorted.  Two objects built
+    independently from the same numbers give equal keys."""
+    import scipy.sparse as sp
+
+    c = sp.csr_matrix(m).astype(np.complex128)  # (a copy: the caller's matrix is not reordered)
+    c.sum_duplicates()
+    c.eliminate_zeros()
+    c.sort_indices()
+    return (tuple(int(v) for v in c.shape), np.asarray(c.indptr, dtype=np.int64), np.asarray(c.indices, dtype=np.int64),
+            np.asarray(c.data))
+
+
 class EnsembleState(DeviceState):
     """The trajectory-averaged state ``mean_b |psi_b><psi_b|`` of a quantum-jump run (``run(mc_ensemble=True)``) at
     one evaluation time, held as what is linear in it and was reduced from the kets on the device: the diagonal
@@ -176,15 +191,25 @@ class EnsembleState(DeviceState):
     ``by_digit`` (multi-level and XY registers, ``run(general_jumps=True, mc_ensemble=True)``): ``{digit:
     {"occupation", "correlation", "occupation_stderr"}}`` for every local state counted, in the order asked for.
     ``occupation``, ``correlation`` and ``occupation_stderr`` are then those of the first digit and need not be given;
-    without it ``by_digit`` is None and the object is that of the two-level route."""
+    without it ``by_digit`` is None and the object is that of the two-level route.
 
-    _REFUSAL = ("the trajectory-averaged density matrix was never formed (mc_ensemble=True keeps its diagonal and "
-                "the means of the built-in observables): run with mc_ensemble=False for {}")
+    ``fidelity`` [F] and ``expectation`` [K] (``run(mc_ensemble_targets=..., mc_ensemble_operators=...)``, in the order
+    registered; empty without them): the trajectory means of ``|<phi_f|psi_b>|^2`` and of ``<psi_b|O_k|psi_b>``, that
+    is ``<phi_f|rho|phi_f>`` and ``Tr(O_k rho)`` of the averaged state, not divided by ``norm2`` either.
+    ``fidelity_stderr`` [F] is the sample standard deviation of the per-trajectory values over sqrt(n_trajectories),
+    ``expectation_stderr`` [K] is ``sqrt((var Re + var Im) / n_trajectories)``.  ``operators`` holds what
+    ``operator_key`` makes of the K operators: ``SimulationResults.expect`` finds a registered one by it."""
+
+    _REFUSAL = ("the trajectory-averaged density matrix was never formed (mc_ensemble=True keeps its diagonal, the "
+                "means of the built-in observables and what the options mc_ensemble_targets / mc_ensemble_operators "
+                "registered before the run): run with mc_ensemble=False for {}")
 
     def __init__(self, diag_sum: np.ndarray, n_trajectories: int, *, occupation: np.ndarray | None = None,
                  correlation: np.ndarray | None = None, energy: float, energy2: float, norm2: float,
                  occupation_stderr: np.ndarray | None = None,
-                 by_digit: "dict[int, dict[str, np.ndarray]] | None" = None) -> None:
+                 by_digit: "dict[int, dict[str, np.ndarray]] | None" = None,
+                 fidelity: Any = (), fidelity_stderr: Any = (), expectation: Any = (), expectation_stderr: Any = (),
+                 operators: Sequence[Any] = ()) -> None:
         d = np.asarray(diag_sum, dtype=np.float64).reshape(-1)
         if n_trajectories < 1:
             raise ValueError(f"n_trajectories must be at least 1, got {n_trajectories}")
@@ -209,6 +234,23 @@ class EnsembleState(DeviceState):
         self.energy2 = float(energy2)
         self.norm2 = float(norm2)
         self.occupation_stderr = np.asarray(occupation_stderr, dtype=np.float64)
+        self.fidelity = np.asarray(fidelity, dtype=np.float64).reshape(-1)
+        self.fidelity_stderr = np.asarray(fidelity_stderr, dtype=np.float64).reshape(-1)
+        self.expectation = np.asarray(expectation, dtype=np.complex128).reshape(-1)
+        self.expectation_stderr = np.asarray(expectation_stderr, dtype=np.float64).reshape(-1)
+        self.operators = tuple(operators)
+        if self.fidelity_stderr.shape != self.fidelity.shape:
+            raise ValueError(f"{self.fidelity.size} fidelities, {self.fidelity_stderr.size} standard errors")
+        if not self.expectation.size == self.expectation_stderr.size == len(self.operators):
+            raise ValueError(f"{self.expectation.size} expectation values, {self.expectation_stderr.size} standard "
+                             f"errors, {len(self.operators)} operators")
+
+    def registered(self, key: Any) -> int | None:
+        """The position of the operator with ``operator_key`` ``key`` among those registered for the run, else None."""
+        for k, own in enumerate(self.operators):
+            if own[0] == key[0] and all(np.array_equal(a, b) for a, b in zip(own[1:], key[1:])):
+                return k
+        return None
 
     @property
     def shape(self) -> tuple[int, int]:
@@ -864,10 +906,24 @@ class SimulationResults(collections.abc.Sequence):
             else:
                 herm = bool(np.allclose(m, m.conj().T))
             if any(isinstance(st, EnsembleState) for st in states):
-                # a trajectory ensemble kept as its diagonal: Tr(m rho) of an exactly diagonal m needs nothing else
+                # a trajectory ensemble kept as its diagonal: Tr(m rho) of an exactly diagonal m needs nothing else; any
+                # other m only when the run reduced it from the kets (run(mc_ensemble_operators=...))
                 if not is_diag:
-                    raise NotImplementedError(EnsembleState._REFUSAL.format("the expectation value of an operator "
-                                                                            "that is not diagonal"))
+                    key = operator_key(m)
+                    found = [st.registered(key) if isinstance(st, EnsembleState) else -1 for st in states]
+                    if any(k is None for k in found):
+                        raise NotImplementedError(EnsembleState._REFUSAL.format(
+                            "the expectation value of an operator that is neither diagonal nor one of the run's "
+                            "mc_ensemble_operators"))
+                    vals = []
+                    for st, k in zip(states, found):
+                        if k >= 0:
+                            vals.append(complex(st.expectation[k]))
+                        else:  # (a state that is no ensemble: the host formula of the loop below)
+                            a = np.asarray(st)
+                            vals.append(np.vdot(a, m @ a) if a.shape[1] == 1 and a.shape[0] > 1 else (m @ a).trace())
+                    out.append(np.array([v.real if herm else v for v in vals]))
+                    continue
                 d = np.asarray(m.diagonal())
                 vals = [np.sum(d * (st.diag() if not st.isket else np.abs(np.asarray(st).reshape(-1)) ** 2))
                         for st in states]

@@ -31,7 +31,7 @@ from .hamiltonian_data import HamiltonianData, SequenceInputs
 from .noise_model import (LEGACY_DEFAULTS, NoiseModel, _NOISE_TYPE_PARAMS,
                           check_eff_noise, has_stochastic_noise)
 from .results import (DeviceState, CoherentResults, EnsembleState, LazyState, NoisyResults, QState, SampledResult,
-                      SimulationResults, SnapshotStore, StateResult)
+                      SimulationResults, SnapshotStore, StateResult, operator_key)
 from .terms import sampling_times
 
 __all__ = ["QutipEmulator", "Solver", "SimConfig", "NoiseModel"]
@@ -234,13 +234,24 @@ class _EnsembleSums:
     """The running sums over the trajectories of an ensemble route (``run(mc_ensemble=True)``): what ``observe_many``
     returns per trajectory - ``[T', B, ...]`` host arrays, not normalised - summed over the trajectory axis per local
     state counted (``digits``; the two-level kernels count local state 0), with the squared occupations for the
-    standard error; :meth:`states` turns them into one ``EnsembleState`` per evaluation time."""
+    standard error; :meth:`states` turns them into one ``EnsembleState`` per evaluation time.
 
-    def __init__(self, n_times: int, n_qudits: int, digits: Any = (0,)) -> None:
+    ``n_targets`` / ``operators`` (``run(mc_ensemble_targets=..., mc_ensemble_operators=...)``; the ``operator_key`` of
+    every operator): :meth:`add_overlaps` sums what ``overlap_many`` and ``expect_sparse`` return per trajectory -
+    ``|z_b|^2`` and its square, ``e_b`` and the squares of its two parts - for ``fidelity`` / ``expectation`` and their
+    standard errors."""
+
+    def __init__(self, n_times: int, n_qudits: int, digits: Any = (0,), n_targets: int = 0,
+                 operators: Any = ()) -> None:
         self.digits = tuple(digits)
         self._n_times = int(n_times)
         self._sums: dict[int, dict[str, np.ndarray]] = {d: {} for d in self.digits}
         self._occ_sq = {d: np.zeros((self._n_times, n_qudits)) for d in self.digits}
+        self._operators = tuple(operators)
+        self._fid = np.zeros((self._n_times, int(n_targets)))  # sum_b |z_b|^2
+        self._fid_sq = np.zeros_like(self._fid)  # sum_b |z_b|^4
+        self._exp = np.zeros((self._n_times, len(self._operators)), dtype=np.complex128)  # sum_b e_b
+        self._exp_sq = np.zeros(self._exp.shape + (2,))  # sum_b (Re e_b)^2, sum_b (Im e_b)^2
 
     def add(self, rows: dict[str, np.ndarray], at: slice, weight: int = 1, digit: int | None = None) -> None:
         """Add the rows of the evaluation times ``at``, each trajectory ``weight`` times (``digit``: the first one)."""
@@ -252,16 +263,38 @@ class _EnsembleSums:
             sums[k][at] += weight * v.sum(axis=1)
         self._occ_sq[digit][at] += weight * (rows["occupation"] ** 2).sum(axis=1)
 
+    def add_overlaps(self, z: np.ndarray, e: np.ndarray, at: slice, weight: int = 1) -> None:
+        """Add the overlaps ``z`` complex[T', B, F] with the targets and the expectation values ``e`` complex[T', B, K]
+        of the operators at the evaluation times ``at``, each trajectory ``weight`` times."""
+        p = z.real * z.real + z.imag * z.imag
+        self._fid[at] += weight * p.sum(axis=1)
+        self._fid_sq[at] += weight * (p * p).sum(axis=1)
+        self._exp[at] += weight * e.sum(axis=1)
+        self._exp_sq[at] += weight * np.stack([(e.real * e.real).sum(axis=1), (e.imag * e.imag).sum(axis=1)], axis=-1)
+
+    @staticmethod
+    def _variance(sum_sq: np.ndarray, mean: np.ndarray, ntraj: int) -> np.ndarray:
+        """The sample variance (ddof = 1) [T, ...] of values with the sum of squares ``sum_sq`` and the mean ``mean``:
+        nan for one trajectory, exactly 0 at the first evaluation time."""
+        if ntraj <= 1:  # (one trajectory has no sample deviation)
+            return np.full_like(sum_sq, np.nan)
+        var = np.maximum(sum_sq - ntraj * mean ** 2, 0.0) / (ntraj - 1)
+        var[0] = 0.0  # every trajectory starts in the same ket (not left to the rounding of sum x^2 - n mean^2)
+        return var
+
     def _means(self, digit: int, ntraj: int) -> dict[str, np.ndarray]:
         """Trajectory means of the pair sums of ``digit`` [T, ...] and the standard error of its occupations."""
         sums, occ_sq = self._sums[digit], self._occ_sq[digit]
         mean_occ = sums["occupation"] / ntraj
-        with np.errstate(invalid="ignore", divide="ignore"):  # (one trajectory has no sample deviation: nan)
-            var = np.maximum(occ_sq - ntraj * mean_occ ** 2, 0.0) / (ntraj - 1) if ntraj > 1 else np.full_like(occ_sq, np.nan)
-            stderr = np.sqrt(var / ntraj)
-        if ntraj > 1:
-            stderr[0] = 0.0  # every trajectory starts in the same ket (not left to the rounding of sum x^2 - n mean^2)
+        stderr = np.sqrt(self._variance(occ_sq, mean_occ, ntraj) / ntraj)
         return {"occupation": mean_occ, "correlation": sums["correlation"] / ntraj, "occupation_stderr": stderr}
+
+    def _overlap_means(self, ntraj: int) -> dict[str, np.ndarray]:
+        """Trajectory means of what :meth:`add_overlaps` summed [T, F] / [T, K] and their standard errors."""
+        fid, exp = self._fid / ntraj, self._exp / ntraj
+        var = self._variance(self._exp_sq[..., 0], exp.real, ntraj) + self._variance(self._exp_sq[..., 1], exp.imag, ntraj)
+        return {"fidelity": fid, "fidelity_stderr": np.sqrt(self._variance(self._fid_sq, fid, ntraj) / ntraj),
+                "expectation": exp, "expectation_stderr": np.sqrt(var / ntraj)}
 
     def states(self, diag_sums: np.ndarray, ntraj: int, with_energy: bool = True,
                by_digit: bool = False) -> list[EnsembleState]:
@@ -270,11 +303,13 @@ class _EnsembleSums:
         states carry the means of every digit, else those of the first one as plain attributes."""
         means = {d: self._means(d, ntraj) for d in self.digits}
         lead, first = self._sums[self.digits[0]], means[self.digits[0]]
+        overlaps = self._overlap_means(ntraj)
         out = []
         for i in range(self._n_times):
             pairs: dict[str, Any] = (
                 {"by_digit": {d: {k: v[i] for k, v in m.items()} for d, m in means.items()}} if by_digit
                 else {k: v[i] for k, v in first.items()})
+            pairs.update({k: v[i] for k, v in overlaps.items()}, operators=self._operators)
             out.append(EnsembleState(diag_sums[i], ntraj, norm2=lead["norm2"][i] / ntraj,
                                      energy=lead["energy"][i] / ntraj if with_energy else math.nan,
                                      energy2=lead["energy2"][i] / ntraj if with_energy else math.nan, **pairs))
@@ -698,6 +733,78 @@ class QutipEmulator:
                     "Can't combine state preparation errors with an initial "
                     "state different from the ground."
                 )
+        if options.get("mc_ensemble_targets") is not None or options.get("mc_ensemble_operators") is not None:
+            self._ensemble_observables(options)  # (a ValueError here: nothing is solved)
+
+    def _ensemble_observables(self, options: dict[str, Any]) -> tuple[np.ndarray, list[Any]]:
+        """The options ``mc_ensemble_targets`` / ``mc_ensemble_operators`` of an ensemble route as (the kets
+        complex128[F, D], the operators as K complex128 CSR matrices [D, D] - duplicates summed, stored zeros dropped,
+        sorted), D = d^N in the run's eigenbasis order; ``ValueError`` for anything else."""
+        import scipy.sparse as sp
+
+        D = self.dim ** self._hamiltonian_data.n_qudits
+        given = options.get("mc_ensemble_targets")
+        items = [] if given is None else list(given)
+        targets = np.zeros((len(items), D), dtype=np.complex128)
+        for f, item in enumerate(items):
+            a = np.asarray(item)
+            if a.dtype.kind not in "biufc":
+                raise ValueError(f"mc_ensemble_targets[{f}] is not numeric (dtype {a.dtype})")
+            if a.ndim == 2 and a.shape[0] == a.shape[1] and a.shape[0] > 1:
+                raise ValueError(f"mc_ensemble_targets[{f}] is a matrix of shape {a.shape}: the ensemble route takes "
+                                 "kets; a mixed target needs the default route (mc_ensemble=False)")
+            if a.shape not in ((D,), (D, 1)):
+                raise ValueError(f"mc_ensemble_targets[{f}] of shape {a.shape} is no ket of {D} amplitudes "
+                                 f"([{D}] or [{D}, 1])")
+            targets[f] = a.reshape(-1)
+        given = options.get("mc_ensemble_operators")
+        operators = []
+        for k, item in enumerate([] if given is None else list(given)):
+            m = SimulationResults._as_operator(item)
+            if m.dtype.kind not in "biufc":
+                raise ValueError(f"mc_ensemble_operators[{k}] is not numeric (dtype {m.dtype})")
+            if tuple(m.shape) != (D, D):
+                raise ValueError(f"mc_ensemble_operators[{k}] of shape {tuple(m.shape)}: expected {(D, D)}")
+            c = sp.csr_matrix(m).astype(np.complex128)
+            c.sum_duplicates()
+            c.eliminate_zeros()
+            c.sort_indices()
+            operators.append(c)
+        return targets, operators
+
+    @staticmethod
+    def _overlap_reducer(sums: _EnsembleSums, targets: np.ndarray, operators: list[Any], device: Any) -> Any:
+        """``reduce(kets [T', B, D] on the device, at, weight=1)`` of an ensemble route: one ``overlap_many`` call with the
+        targets and one ``expect_sparse`` call per operator over the ``T' B`` kets as one stack, summed into ``sums``
+        (``_EnsembleSums.add_overlaps``).  The targets and the operators' non-zeros are uploaded here, once per run;
+        with nothing registered nothing is launched."""
+        from .engine import expect_sparse, overlap_many, sparse_triplets
+
+        n_f, n_k, dim = len(targets), len(operators), int(targets.shape[1])
+        if not n_f and not n_k:
+            return lambda kets, at, weight=1: None
+        import torch
+
+        targets_dev = torch.from_numpy(targets).to(device) if n_f else None
+        triplets = [sparse_triplets(m, dim, device) for m in operators]
+
+        def reduce(kets: Any, at: slice, weight: int = 1) -> None:
+            n_t, n_b = int(kets.shape[0]), int(kets.shape[1])
+            flat = kets.reshape(n_t * n_b, dim)
+            # (the norms that come with the overlaps are not needed: norm2 is observe_many's)
+            z = overlap_many(flat, targets_dev)[0].cpu().numpy() if n_f else np.zeros((n_t * n_b, 0), dtype=complex)
+            e = (torch.stack([expect_sparse(flat, t) for t in triplets], dim=1).cpu().numpy() if n_k
+                 else np.zeros((n_t * n_b, 0), dtype=complex))
+            sums.add_overlaps(z.reshape(n_t, n_b, n_f), e.reshape(n_t, n_b, n_k), at, weight)
+
+        return reduce
+
+    @staticmethod
+    def _overlap_bytes(targets: np.ndarray, operators: list[Any], chunk: int) -> tuple[int, int]:
+        """Device bytes of what :meth:`_overlap_reducer` keeps (per evaluation time: the overlaps and expectation
+        values of one chunk; once per run: the targets and the operators' triplets), for the snapshot budget."""
+        return (16 * chunk * (len(targets) + len(operators)),
+                int(targets.nbytes) + sum(24 * int(m.nnz) for m in operators))
 
     def _solver_mode(self, problem: dict[str, Any]) -> str:
         """simulation.py:705-718."""
@@ -995,14 +1102,16 @@ class QutipEmulator:
     _DEVICE_STATE_BYTES = 1 << 30
 
     @staticmethod
-    def _check_snapshot_budget(n_snapshots: int, state_bytes: int, what: str = "density matrix") -> None:
+    def _check_snapshot_budget(n_snapshots: int, state_bytes: int, what: str = "density matrix",
+                               once_bytes: int = 0) -> None:
         """Refuse evaluation-time lists whose stored states cannot fit the device (the reference
         would fail the same way in host memory, after hours): the solver needs 4 work copies, the
-        results one copy per evaluation time."""
+        results one copy per evaluation time.  ``once_bytes``: what the run keeps on the device once, whatever the
+        number of evaluation times (the targets and operators of an ensemble route)."""
         import torch
 
         free, total = torch.cuda.mem_get_info()
-        need = (n_snapshots + 5) * state_bytes
+        need = (n_snapshots + 5) * state_bytes + once_bytes
         if need > 0.9 * free:
             raise MemoryError(
                 f"Storing the state at {n_snapshots} evaluation times needs {need / 2**30:.0f} GiB of "
@@ -1106,8 +1215,10 @@ class QutipEmulator:
                 "solver=Solver.MESOLVER with a density matrix.")
         chunk = int(max(1, min(ntraj, 1024, (2 << 30) // max(1, D * 16 * len(times)))))
         # per evaluation time: one row of the diagonals and the kets of one chunk (the solver's work copies are kets too)
-        self._check_snapshot_budget(len(times) - 1, D * 8 + chunk * D * 16,
-                                    "evaluation time (the ensemble diagonal and one chunk of kets)")
+        targets, operators = self._ensemble_observables(options)
+        per_time, once = self._overlap_bytes(targets, operators, chunk)
+        self._check_snapshot_budget(len(times) - 1, D * 8 + chunk * D * 16 + per_time,
+                                    "evaluation time (the ensemble diagonal and one chunk of kets)", once)
         observer = options.get("mc_ensemble_observer")
         own_observer = observer is None
         if own_observer:
@@ -1115,15 +1226,17 @@ class QutipEmulator:
             noiseless["collapse_ops"] = []
             observer = Engine.from_problems([noiseless], mode="sesolve")
         t_us = np.asarray(times, dtype=np.float64)
-        sums = _EnsembleSums(len(times), n)
+        sums = _EnsembleSums(len(times), n, n_targets=len(targets), operators=[operator_key(m) for m in operators])
         add = sums.add
         try:
             torch = observer.torch
+            overlaps = self._overlap_reducer(sums, targets, operators, observer.device)
             diag = torch.zeros((len(times), D), dtype=torch.float64, device=observer.device)
             first = observer.new_state(init.reshape(1, -1))[None]  # [1, 1, D]: every trajectory starts here
             ensemble_diag(first, diag[:1])
             diag[0] *= ntraj
             add(observer.observe_many(first, t_us[:1], energy=True), slice(0, 1), ntraj)
+            overlaps(first, slice(0, 1), ntraj)
             del first
             done = 0
             jumps = []
@@ -1136,6 +1249,7 @@ class QutipEmulator:
                                          **self._engine_kwargs(options))
                     ensemble_diag(snaps, diag[1:])
                     add(observer.observe_many(snaps, t_us[1:], energy=True), slice(1, None))
+                    overlaps(snaps, slice(1, None))
                     jumps.append(eng.mc_jumps())
                     self.last_engine_stats = eng.stats()
                     del state, snaps
@@ -1200,8 +1314,10 @@ class QutipEmulator:
         D = tables.dim
         chunk = int(max(1, min(ntraj, 1024, (2 << 30) // max(1, D * 16 * len(times)))))
         # per evaluation time: one row of the diagonals and the kets of one chunk (the solver's work copies are kets too)
-        self._check_snapshot_budget(len(times) - 1, D * 8 + chunk * D * 16,
-                                    "evaluation time (the ensemble diagonal and one chunk of kets)")
+        targets, operators = self._ensemble_observables(options)
+        per_time, once = self._overlap_bytes(targets, operators, chunk)
+        self._check_snapshot_budget(len(times) - 1, D * 8 + chunk * D * 16 + per_time,
+                                    "evaluation time (the ensemble diagonal and one chunk of kets)", once)
         observer = options.get("mc_ensemble_observer")
         own_observer = observer is None
         if own_observer:
@@ -1209,9 +1325,10 @@ class QutipEmulator:
             noiseless["collapse_ops"] = []
             observer = GeneralEngine(lower_general(noiseless, mesolve=False, matrix_free=True))
         t_us = np.asarray(times, dtype=np.float64)
-        sums = _EnsembleSums(len(times), n, digits)
+        sums = _EnsembleSums(len(times), n, digits, n_targets=len(targets), operators=[operator_key(m) for m in operators])
         try:
             with_energy = observer.apply_path() in ("fused", "fused_lds")
+            overlaps = self._overlap_reducer(sums, targets, operators, observer.device)
 
             def observe(kets: Any, t: np.ndarray, at: slice, weight: int = 1) -> None:
                 for k, digit in enumerate(digits):  # (only the first call carries the energy moments)
@@ -1223,6 +1340,7 @@ class QutipEmulator:
             ensemble_diag(first, diag[:1])
             diag[0] *= ntraj
             observe(first, t_us[:1], slice(0, 1), ntraj)
+            overlaps(first, slice(0, 1), ntraj)
             del first
             done = 0
             jumps = []
@@ -1234,6 +1352,7 @@ class QutipEmulator:
                     snaps = eng.mc_solve(state, times, self._mc_seeds(b, options), **kw)
                     ensemble_diag(snaps, diag[1:])
                     observe(snaps, t_us[1:], slice(1, None))
+                    overlaps(snaps, slice(1, None))
                     jumps.append(eng.mc_jumps())
                     self.last_engine_stats = eng.stats()
                     del state, snaps
@@ -1429,10 +1548,22 @@ class QutipEmulator:
         (sampling, ``sampling_dist``, the SPAM flips and ``expect`` of diagonal operators work unchanged) and the
         trajectory means ``occupation``, ``correlation``, ``energy``, ``energy2``, ``norm2`` with
         ``occupation_stderr``, equal to the values of the averaged matrix within rounding.  ``full()``, ``overlap``
-        and ``expect`` of other operators raise ``NotImplementedError``.  Every other run ignores the option
-        (but see ``general_jumps`` with it, below).
+        and ``expect`` of other operators raise ``NotImplementedError`` (but see ``mc_ensemble_operators``).  Every
+        other run ignores the option (but see ``general_jumps`` with it, below).
         ``mc_ensemble_observer``: a noiseless batch-1 sesolve ``Engine`` whose H(t) the energy moments use (left
         open); by default one is built from the run's problem without its collapse operators.
+        ``mc_ensemble_targets``: F kets, ``[F, D]`` or a list of ``[D]`` / ``[D, 1]`` arrays (D = d^N, the run's
+        eigenbasis order): ``EnsembleState.fidelity`` [F] is the fidelity ``<phi|rho|phi>`` of the averaged state with
+        each, the trajectory mean of ``|<phi|psi_b>|^2`` (one ``overlap_many`` call per chunk of trajectories), and
+        ``fidelity_stderr`` its Monte-Carlo error.  A matrix (a mixed target) raises ``ValueError``: it needs the
+        default route.
+        ``mc_ensemble_operators``: K operators of shape ``(D, D)`` - arrays, SciPy sparse matrices or ``qutip.Qobj``,
+        as ``results.expect`` takes them: ``EnsembleState.expectation`` [K] is ``Tr(O rho)``, the trajectory mean of
+        ``<psi_b|O|psi_b>`` (one ``expect_sparse`` call per operator and chunk), with ``expectation_stderr``;
+        ``results.expect`` then serves these operators - recognised by their shape and stored non-zeros - next to
+        the diagonal ones.  Neither value is divided by ``norm2``.  Both options are used by the two ensemble routes
+        alone and ignored by every other run; a wrong shape or a non-numeric entry raises ``ValueError`` before
+        anything is solved.
 
         ``general_jumps=True`` with ``mc_ensemble=True``: the same for the deterministic-noise run of the general
         path (multi-level bases, XY mode, a non-diagonal ``sum C^dag C``): the trajectories of ``general_jumps=True``
