@@ -10,7 +10,7 @@ from .hamiltonian_data import (ChannelInput, HamiltonianData, SequenceInputs,
                                Slot, single_global_channel)
 from .noise_model import NoiseModel
 from .results import (CoherentResults, NoisyResults, QState, SampledResult,
-                      SimulationResults, StateResult)
+                      SimulationResults, StateResult, entropy_vn)
 from .simulation import QutipEmulator, SimConfig, Solver
 from .batch import run_batch
 from . import backend
@@ -21,7 +21,7 @@ __version__ = "0.1.0"
 
 __all__ = [
     "QutipEmulator", "Solver", "SimConfig", "NoiseModel", "CoherentResults",
-    "NoisyResults", "SimulationResults", "StateResult", "SampledResult", "QState",
+    "NoisyResults", "SimulationResults", "StateResult", "SampledResult", "QState", "entropy_vn",
     "SequenceInputs", "ChannelInput", "Slot", "HamiltonianData", "single_global_channel",
     "QutipBackendV2", "RydEmuBackend", "register_with_pulser", "QutipBackend", "EmulatorConfig", "QutipConfig", "RydState", "RydOperator", "Results", "backend",
     "run_batch",

@@ -85,4 +85,5 @@ SPLITR_INSTANCES_14(SPLITR_EXTERN)
 #include "host_mc_general.hpp"
 #include "host_observables.hpp"
 #include "k_ensemble.hpp"
+#include "k_ptrace.hpp"
 #include "host_replay.hpp"

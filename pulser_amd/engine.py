@@ -137,6 +137,116 @@ def ensemble_diag(states: Any, diag: Any) -> None:
         torch.cuda.current_stream(states.device).cuda_stream))
 
 
+REDUCED_DENSITY_MAX_ROWS = 64  # dA of ryd_reduced_density at most: six qubits, three qutrits, three four-level atoms
+
+
+def check_keep(keep: Any, n_sites: int) -> tuple[int, ...]:
+    """``keep`` (any iterable of ints: the sites of a subsystem) sorted, as a tuple.  ``ValueError`` when it is empty,
+    holds something that is no integer, a duplicate, or a site outside ``0 .. n_sites - 1``."""
+    try:
+        raw = list(keep)
+    except TypeError:
+        raise ValueError(f"keep must be an iterable of site indices, got {keep!r}") from None
+    if not raw:
+        raise ValueError("keep is empty: a subsystem needs at least one site")
+    if not all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) for k in raw):
+        raise ValueError(f"keep must hold integers, got {raw!r}")
+    sites = tuple(sorted(int(k) for k in raw))
+    if len(set(sites)) != len(sites):
+        raise ValueError(f"keep holds a site twice: {raw!r}")
+    if sites[0] < 0 or sites[-1] >= n_sites:
+        raise ValueError(f"keep {raw!r} holds a site outside 0 .. {n_sites - 1}")
+    return sites
+
+
+def sites_of_dim(dim: int, local_dim: int) -> int:
+    """n with ``local_dim**n == dim``; ``ValueError`` when there is none."""
+    if local_dim < 2:
+        raise ValueError(f"local_dim must be at least 2, got {local_dim}")
+    n, d = 0, 1
+    while d < dim:
+        d *= local_dim
+        n += 1
+    if d != dim or n < 1:
+        raise ValueError(f"the dimension {dim} is not a power (>= 1) of local_dim = {local_dim}")
+    return n
+
+
+def reduced_density(states: Any, keep: Any, local_dim: int = 2, out: Any = None, n_split: int = 0) -> Any:
+    """``out[t, a, a'] += sum_b sum_r psi(t, b)[idx(a, r)] conj psi(t, b)[idx(a', r)]`` on the device
+    (``ryd_reduced_density``): the partial trace ``Tr_rest |psi><psi|`` of every ket over the sites ``keep``, summed
+    over axis 1 - what ``Qobj.ptrace(keep)`` gives for the states of a run, without a state leaving the device.
+
+    ``states`` is a complex128 CUDA tensor ``[T, B >= 1, D]`` with ``D = local_dim**n`` (``local_dim`` 2, 3 or 4), or a
+    view of one whose last axis is contiguous (the strides of the first two axes are passed on, as for
+    ``ensemble_diag``); a caller who wants one matrix per ``(t, b)`` passes ``x.reshape(T * B, 1, D)``.  Site 0 is the
+    most significant digit.  ``keep`` is any iterable of distinct sites; it is sorted, and row ``a`` of the result is
+    the number formed by the kept digits in ascending site order.  ``dA = local_dim**len(keep)`` is at most 64.
+
+    Returns ``out``, complex128 ``[T, dA, dA]`` contiguous on the same device: a new zero tensor when none is given,
+    else the one given, which is ACCUMULATED into (call once per chunk of trajectories).  Both triangles are written,
+    exactly conjugate to each other.  ``n_split`` workgroups share one time: 1 is one workgroup per time, 0 lets the
+    library choose.  A scratch tensor is allocated only when a split is used: ``T * n_split * dA * dA`` complex128 for
+    a given ``n_split > 1``, and for ``n_split = 0`` at most ``min(1024 // T, D // 512)`` such partials per time
+    (none when that is below 2: the library then takes one workgroup per time).  No atomics: repeated calls with the
+    same ``n_split`` give bitwise equal results."""
+    torch = _torch()
+    if not (isinstance(states, torch.Tensor) and states.is_cuda):
+        raise ValueError("states must be a CUDA tensor")
+    if states.dtype != torch.complex128:
+        raise TypeError(f"a complex128 states tensor expected, got {states.dtype}")
+    if states.dim() != 3 or int(states.shape[1]) < 1 or int(states.shape[2]) < 1:
+        raise ValueError(f"shape {tuple(states.shape)} does not match [T, B >= 1, D]")
+    n_t, n_b, dim = (int(v) for v in states.shape)
+    if int(local_dim) not in (2, 3, 4):
+        raise ValueError(f"local_dim must be 2, 3 or 4, got {local_dim}")
+    local_dim = int(local_dim)
+    n_sites = sites_of_dim(dim, local_dim)
+    sites = check_keep(keep, n_sites)
+    d_a = local_dim ** len(sites)
+    if d_a > REDUCED_DENSITY_MAX_ROWS:
+        raise ValueError(f"{len(sites)} sites of local dimension {local_dim} make a {d_a} x {d_a} matrix: the device "
+                         f"partial trace serves at most {REDUCED_DENSITY_MAX_ROWS} rows")
+    if out is None:
+        out = torch.zeros((n_t, d_a, d_a), dtype=torch.complex128, device=states.device)
+    else:
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == states.device):
+            raise ValueError("states and out must be CUDA tensors on the same device")
+        if out.dtype != torch.complex128:
+            raise TypeError(f"a complex128 out tensor expected, got {out.dtype}")
+        if tuple(out.shape) != (n_t, d_a, d_a):
+            raise ValueError(f"out has the shape {tuple(out.shape)}, expected {(n_t, d_a, d_a)}")
+        if not out.is_contiguous():
+            raise ValueError("a contiguous out tensor expected")
+    n_split = int(n_split)
+    if n_split < 0:
+        raise ValueError(f"n_split must be 0 (the library's choice) or positive, got {n_split}")
+    if n_t == 0:
+        return out
+    if states.stride(2) != 1 and dim > 1:
+        raise ValueError("the last axis of states must be contiguous (the first two may be strided)")
+    # (the stride of an axis of length 1 is arbitrary in torch and never used: any valid value will do)
+    stride_b = int(states.stride(1)) if n_b > 1 else dim
+    stride_t = int(states.stride(0)) if n_t > 1 else max(n_b * stride_b, dim)
+    if stride_b < dim or stride_t < dim:
+        raise ValueError(f"strides {stride_t} / {stride_b} of the first two axes are smaller than a state ({dim})")
+    parts = n_split
+    if n_split == 0:
+        parts = min(1024 // n_t, dim // 512)
+        if parts < 2:
+            n_split, parts = 1, 1
+    scratch = None
+    if parts > 1:
+        scratch = torch.empty((n_t, parts, d_a, d_a), dtype=torch.complex128, device=states.device)
+    keep_arr = np.ascontiguousarray(sites, dtype=np.int32)
+    _lib.check(_lib.load().ryd_reduced_density(
+        states.data_ptr(), n_t, n_b, stride_t, stride_b, dim, local_dim, n_sites, keep_arr.ctypes.data, len(sites),
+        out.data_ptr(), n_split, None if scratch is None else scratch.data_ptr(),
+        0 if scratch is None else scratch.numel() * 16, int(states.device.index or 0),
+        torch.cuda.current_stream(states.device).cuda_stream))
+    return out
+
+
 def accumulate(x: Any, acc: Any, weight: float = 1.0) -> None:
     """``acc += weight * x`` elementwise on the device (``ryd_accumulate``): the running sum of
     trajectory density matrices of aggregators.py:29-35."""

@@ -85,6 +85,46 @@ class QState(np.ndarray):
             return complex(np.vdot(b, a @ b))
         return complex(np.trace(a.conj().T @ b))
 
+    def ptrace(self, keep: Any, local_dim: int = 2) -> "QState":
+        """The reduced density matrix of the sites ``keep`` (``Qobj.ptrace``): ``Tr_rest |psi><psi|`` of a ket,
+        ``Tr_rest rho`` of a density matrix, as an operator of dimension ``local_dim**len(keep)``.
+
+        The convention is this package's own: site 0 is the most significant digit of the state's index (stride
+        ``local_dim**(n - 1 - k)``), ``keep`` is sorted, and the row index is the number formed by the kept digits in
+        ascending site order.  ``n`` is inferred from the dimension (``ValueError`` when it is no power of
+        ``local_dim``); an empty ``keep``, a duplicate or a site out of range raise ``ValueError``."""
+        return QState(_ptrace_host(np.asarray(self), self.isket, keep, int(local_dim)))
+
+
+def _ptrace_host(a: np.ndarray, isket: bool, keep: Any, d: int) -> np.ndarray:
+    """The host formula of every ``ptrace``: a reshape to ``[d] * n``, a transpose that brings the kept digits to the
+    front, and one matmul (kets) or one trace over the paired rest axes (density matrices)."""
+    from .engine import check_keep, sites_of_dim
+
+    n = sites_of_dim(int(a.shape[0]), d)
+    sites = check_keep(keep, n)
+    rest = tuple(k for k in range(n) if k not in sites)
+    d_a = d ** len(sites)
+    if isket:
+        m = a.reshape((d,) * n).transpose(sites + rest).reshape(d_a, -1)
+        return m @ m.conj().T
+    r = a.reshape((d,) * (2 * n)).transpose(sites + tuple(n + k for k in sites) + rest + tuple(n + k for k in rest))
+    r = r.reshape(d_a, d_a, d ** len(rest), d ** len(rest))
+    return np.trace(r, axis1=2, axis2=3)
+
+
+def entropy_vn(rho: Any, base: float = 2.0) -> float:
+    """The von Neumann entropy ``-Tr(p log p)`` of ``p = rho / Tr rho`` in units of ``log(base)`` (bits by default):
+    ``eigvalsh`` of the normalised matrix, eigenvalues below 0 (rounding) clipped to 0, ``0 log 0 = 0``."""
+    m = np.asarray(rho, dtype=complex)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError(f"a square matrix expected, got the shape {m.shape}")
+    w = np.linalg.eigvalsh(m / np.trace(m).real)
+    w = np.clip(w, 0.0, None)
+    w = w[w > 0.0]
+    s = float(-np.sum(w * np.log(w)) / np.log(base))
+    return s if s > 0.0 else 0.0  # (also turns -0.0 of a pure state into 0.0)
+
 
 class DeviceState:
     """A density matrix that stays on the GPU (mesolve at 13+ atoms: 1 - 4 GiB per state).
@@ -153,6 +193,13 @@ class DeviceState:
     def overlap(self, other: Any) -> complex:
         return QState(self.full()).overlap(other)
 
+    def ptrace(self, keep: Any, local_dim: int = 2) -> "QState":
+        """``QState.ptrace`` of this state.  The ket form is traced as a ket (the matrix is not expanded); a density
+        matrix on the device is copied to the host first: the device partial trace serves kets only."""
+        if self._ket is not None:
+            return QState(_ptrace_host(self._ket.reshape(-1, 1), True, keep, int(local_dim)))
+        return QState(_ptrace_host(self.full(), False, keep, int(local_dim)))
+
     def __repr__(self) -> str:
         where = "device tensor" if self._tensor is not None else "ket form"
         return f"DeviceState(shape={self.shape}, {where})"
@@ -198,18 +245,24 @@ class EnsembleState(DeviceState):
     is ``<phi_f|rho|phi_f>`` and ``Tr(O_k rho)`` of the averaged state, not divided by ``norm2`` either.
     ``fidelity_stderr`` [F] is the sample standard deviation of the per-trajectory values over sqrt(n_trajectories),
     ``expectation_stderr`` [K] is ``sqrt((var Re + var Im) / n_trajectories)``.  ``operators`` holds what
-    ``operator_key`` makes of the K operators: ``SimulationResults.expect`` finds a registered one by it."""
+    ``operator_key`` makes of the K operators: ``SimulationResults.expect`` finds a registered one by it.
+
+    ``subsystems`` (sorted site tuples) and ``reduced`` (``run(mc_ensemble_subsystems=...)``; empty without it):
+    ``reduced[k]`` is given as the trajectory SUM of ``Tr_rest |psi_b><psi_b|`` over the sites ``subsystems[k]``
+    (``ryd_reduced_density``) and held divided by ``n_trajectories``, like the diagonal and not divided by ``norm2``;
+    ``ptrace`` serves these and refuses every other subsystem."""
 
     _REFUSAL = ("the trajectory-averaged density matrix was never formed (mc_ensemble=True keeps its diagonal, the "
-                "means of the built-in observables and what the options mc_ensemble_targets / mc_ensemble_operators "
-                "registered before the run): run with mc_ensemble=False for {}")
+                "means of the built-in observables and what the options mc_ensemble_targets / mc_ensemble_operators / "
+                "mc_ensemble_subsystems registered before the run): run with mc_ensemble=False for {}")
 
     def __init__(self, diag_sum: np.ndarray, n_trajectories: int, *, occupation: np.ndarray | None = None,
                  correlation: np.ndarray | None = None, energy: float, energy2: float, norm2: float,
                  occupation_stderr: np.ndarray | None = None,
                  by_digit: "dict[int, dict[str, np.ndarray]] | None" = None,
                  fidelity: Any = (), fidelity_stderr: Any = (), expectation: Any = (), expectation_stderr: Any = (),
-                 operators: Sequence[Any] = ()) -> None:
+                 operators: Sequence[Any] = (), subsystems: Sequence[tuple[int, ...]] = (),
+                 reduced: Sequence[np.ndarray] = ()) -> None:
         d = np.asarray(diag_sum, dtype=np.float64).reshape(-1)
         if n_trajectories < 1:
             raise ValueError(f"n_trajectories must be at least 1, got {n_trajectories}")
@@ -244,6 +297,13 @@ class EnsembleState(DeviceState):
         if not self.expectation.size == self.expectation_stderr.size == len(self.operators):
             raise ValueError(f"{self.expectation.size} expectation values, {self.expectation_stderr.size} standard "
                              f"errors, {len(self.operators)} operators")
+        self.subsystems = tuple(tuple(sorted(int(k) for k in sub)) for sub in subsystems)
+        self.reduced = tuple(np.asarray(m, dtype=np.complex128) / self.n_trajectories for m in reduced)
+        if len(self.reduced) != len(self.subsystems):
+            raise ValueError(f"{len(self.subsystems)} subsystems, {len(self.reduced)} reduced density matrices")
+        for sub, m in zip(self.subsystems, self.reduced):
+            if m.ndim != 2 or m.shape[0] != m.shape[1]:
+                raise ValueError(f"the reduced density matrix of {sub} has the shape {m.shape}")
 
     def registered(self, key: Any) -> int | None:
         """The position of the operator with ``operator_key`` ``key`` among those registered for the run, else None."""
@@ -282,6 +342,18 @@ class EnsembleState(DeviceState):
 
     def overlap(self, other: Any) -> complex:
         return self._refuse("overlap()")
+
+    def ptrace(self, keep: Any, local_dim: int = 2) -> "QState":
+        """The reduced density matrix ``mean_b Tr_rest |psi_b><psi_b|`` of a subsystem registered for the run
+        (``run(mc_ensemble_subsystems=...)``; not divided by ``norm2``), in any order of its sites; any other is
+        refused."""
+        try:
+            key = tuple(sorted(int(k) for k in keep))
+        except TypeError:
+            key = None
+        if key in self.subsystems:
+            return QState(self.reduced[self.subsystems.index(key)])
+        return self._refuse("ptrace() of a subsystem that is not one of the run's mc_ensemble_subsystems")
 
     def __repr__(self) -> str:
         return f"EnsembleState(shape={self.shape}, n_trajectories={self.n_trajectories})"
@@ -466,6 +538,20 @@ class LazyState:
     def __array__(self, dtype: Any = None, copy: Any = None) -> np.ndarray:
         a = np.asarray(self._materialise())
         return a if dtype is None else a.astype(dtype)
+
+    def ptrace(self, keep: Any, local_dim: int = 2) -> QState:
+        """``QState.ptrace`` of this state.  A ket that is still a snapshot on a GPU is traced there
+        (``engine.reduced_density``, at most 64 rows): the state stays a snapshot, the call is no read of the store and
+        only the matrix crosses PCIe.  Anything else takes the host formula on the materialised state."""
+        from .engine import REDUCED_DENSITY_MAX_ROWS, check_keep, reduced_density, sites_of_dim
+
+        dev = self.device_tensor
+        if self._q is None and self.isket and dev is not None and getattr(dev, "is_cuda", False) and dev.dim() == 1 \
+                and int(local_dim) in (2, 3, 4):
+            sites = check_keep(keep, sites_of_dim(self._shape[0], int(local_dim)))
+            if int(local_dim) ** len(sites) <= REDUCED_DENSITY_MAX_ROWS:
+                return QState(reduced_density(dev.reshape(1, 1, -1), sites, int(local_dim))[0].cpu().numpy())
+        return self._materialise().ptrace(keep, local_dim)
 
     def __getattr__(self, name: str) -> Any:  # full, dag, diag, tr, norm, unit, overlap, copy, conj, T, real, ...
         if name.startswith("_"):
@@ -947,6 +1033,59 @@ class SimulationResults(collections.abc.Sequence):
                 vals.append(v.real if herm else v)
             out.append(np.array(vals))
         return out
+
+    def reduced_states(self, keep: Any, normalize: bool = False) -> np.ndarray:
+        """The reduced density matrix of the sites ``keep`` (``QState.ptrace``: ascending site order, site 0 the most
+        significant digit) at every evaluation time: ``[len(self), dA, dA]`` complex, ``dA = dim**len(keep)`` with the
+        local dimension of the run's basis.  ``normalize=True`` divides each matrix by its trace.
+
+        The states that are still ket snapshots of one store on a GPU are traced there in ONE ``engine.reduced_density``
+        call over the store's tensor (a strided view when they are consecutive or every k-th time, else a gathered
+        copy): nothing counts as a read of the store and only the matrices cross PCIe.  The host formula serves the
+        rest - the initial state, states read earlier, density matrices, ``dA`` above 64.  States of a quantum-jump
+        ensemble (``EnsembleState``) answer for the subsystems registered with ``run(mc_ensemble_subsystems=...)``
+        and refuse any other."""
+        if self._use_pseudo_dens:
+            raise NotImplementedError("reduced_states() is not available for results that hold samples only")
+        from .engine import REDUCED_DENSITY_MAX_ROWS, check_keep, reduced_density
+
+        d = self._dim
+        sites = check_keep(keep, self._size)
+        d_a = d ** len(sites)
+        states = self.states
+        out = np.empty((len(states), d_a, d_a), dtype=complex)
+        done = [False] * len(states)
+        live = [st for st in states if isinstance(st, LazyState) and st._q is None and st.isket and st._store is not None
+                and st._store.device_tensor is not None]
+        if live and d_a <= REDUCED_DENSITY_MAX_ROWS and d in (2, 3, 4):
+            store, b = live[0]._store, live[0]._b
+            dev = store.device_tensor
+            if getattr(dev, "is_cuda", False) and dev.dim() == 3 and int(dev.shape[2]) == d ** self._size:
+                pos = [i for i, st in enumerate(states) if isinstance(st, LazyState) and st._q is None
+                       and st._store is store and st._b == b]
+                idx = np.array([states[i]._i for i in pos], dtype=np.int64)
+                step = int(idx[1] - idx[0]) if len(idx) > 1 else 1
+                if len(idx) == 1 or (step >= 1 and np.all(np.diff(idx) == step)):  # a strided view, no copy
+                    x = dev[int(idx[0]):int(idx[-1]) + 1:step, b]
+                else:
+                    import torch
+
+                    x = dev[torch.from_numpy(idx).to(dev.device), b]
+                host = reduced_density(x.unsqueeze(1), sites, d).cpu().numpy()
+                for k, i in enumerate(pos):
+                    out[i] = host[k]
+                    done[i] = True
+        for i, st in enumerate(states):
+            if not done[i]:
+                out[i] = np.asarray(st.ptrace(sites, d) if hasattr(st, "ptrace") else QState(st).ptrace(sites, d))
+        if normalize:
+            out /= np.trace(out, axis1=1, axis2=2)[:, None, None]
+        return out
+
+    def entanglement_entropy(self, keep: Any, base: float = 2.0) -> np.ndarray:
+        """``entropy_vn`` of ``reduced_states(keep)`` at every evaluation time, ``[len(self)]`` floats: for a pure
+        state the entanglement entropy between the sites ``keep`` and the rest, in bits by default."""
+        return np.array([entropy_vn(r, base) for r in self.reduced_states(keep)])
 
     def to_host(self) -> "SimulationResults":
         """Move the stored states of this run from HBM to host memory now (what the reference always does,

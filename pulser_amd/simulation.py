@@ -297,10 +297,12 @@ class _EnsembleSums:
                 "expectation": exp, "expectation_stderr": np.sqrt(var / ntraj)}
 
     def states(self, diag_sums: np.ndarray, ntraj: int, with_energy: bool = True,
-               by_digit: bool = False) -> list[EnsembleState]:
+               by_digit: bool = False, subsystems: Any = (), reduced_sums: Any = ()) -> list[EnsembleState]:
         """One ``EnsembleState`` per evaluation time from the summed diagonals ``diag_sums`` [T, D]; the norm and the
         energy moments are those that came with the first digit (``with_energy=False``: nan).  ``by_digit``: the
-        states carry the means of every digit, else those of the first one as plain attributes."""
+        states carry the means of every digit, else those of the first one as plain attributes.  ``subsystems`` /
+        ``reduced_sums`` (``run(mc_ensemble_subsystems=...)``): site tuples and, for each, the trajectory sums
+        ``[T, dA, dA]`` of its reduced density matrices."""
         means = {d: self._means(d, ntraj) for d in self.digits}
         lead, first = self._sums[self.digits[0]], means[self.digits[0]]
         overlaps = self._overlap_means(ntraj)
@@ -310,6 +312,8 @@ class _EnsembleSums:
                 {"by_digit": {d: {k: v[i] for k, v in m.items()} for d, m in means.items()}} if by_digit
                 else {k: v[i] for k, v in first.items()})
             pairs.update({k: v[i] for k, v in overlaps.items()}, operators=self._operators)
+            if len(subsystems):
+                pairs.update(subsystems=subsystems, reduced=[r[i] for r in reduced_sums])
             out.append(EnsembleState(diag_sums[i], ntraj, norm2=lead["norm2"][i] / ntraj,
                                      energy=lead["energy"][i] / ntraj if with_energy else math.nan,
                                      energy2=lead["energy2"][i] / ntraj if with_energy else math.nan, **pairs))
@@ -735,6 +739,28 @@ class QutipEmulator:
                 )
         if options.get("mc_ensemble_targets") is not None or options.get("mc_ensemble_operators") is not None:
             self._ensemble_observables(options)  # (a ValueError here: nothing is solved)
+        if options.get("mc_ensemble_subsystems") is not None:
+            self._ensemble_subsystems(options)  # (the same)
+
+    def _ensemble_subsystems(self, options: dict[str, Any]) -> list[tuple[int, ...]]:
+        """The option ``mc_ensemble_subsystems`` as sorted site tuples (positions in ``samples_obj.qubit_ids``);
+        ``ValueError`` for an entry that is empty, holds something that is no integer, a duplicate or a site out of
+        range, or makes more rows than the device partial trace serves (2^k <= 64)."""
+        from .engine import REDUCED_DENSITY_MAX_ROWS, check_keep
+
+        given = options.get("mc_ensemble_subsystems")
+        n = self._hamiltonian_data.n_qudits
+        out = []
+        for k, item in enumerate([] if given is None else list(given)):
+            try:
+                sites = check_keep(item, n)
+            except ValueError as exc:
+                raise ValueError(f"mc_ensemble_subsystems[{k}]: {exc}") from None
+            if 2 ** len(sites) > REDUCED_DENSITY_MAX_ROWS:
+                raise ValueError(f"mc_ensemble_subsystems[{k}] holds {len(sites)} sites: the reduced density matrix "
+                                 f"of an ensemble has at most {REDUCED_DENSITY_MAX_ROWS} rows (6 two-level atoms)")
+            out.append(sites)
+        return out
 
     def _ensemble_observables(self, options: dict[str, Any]) -> tuple[np.ndarray, list[Any]]:
         """The options ``mc_ensemble_targets`` / ``mc_ensemble_operators`` of an ensemble route as (the kets
@@ -1217,6 +1243,9 @@ class QutipEmulator:
         # per evaluation time: one row of the diagonals and the kets of one chunk (the solver's work copies are kets too)
         targets, operators = self._ensemble_observables(options)
         per_time, once = self._overlap_bytes(targets, operators, chunk)
+        subsystems = self._ensemble_subsystems(options)
+        # (one [dA, dA] accumulator per subsystem and evaluation time, and as much again for the partials of a split)
+        per_time += sum(2 * 16 * 4 ** len(sub) for sub in subsystems)
         self._check_snapshot_budget(len(times) - 1, D * 8 + chunk * D * 16 + per_time,
                                     "evaluation time (the ensemble diagonal and one chunk of kets)", once)
         observer = options.get("mc_ensemble_observer")
@@ -1227,6 +1256,7 @@ class QutipEmulator:
             observer = Engine.from_problems([noiseless], mode="sesolve")
         t_us = np.asarray(times, dtype=np.float64)
         sums = _EnsembleSums(len(times), n, n_targets=len(targets), operators=[operator_key(m) for m in operators])
+        reduced_host: list[np.ndarray] = []
         add = sums.add
         try:
             torch = observer.torch
@@ -1237,6 +1267,16 @@ class QutipEmulator:
             diag[0] *= ntraj
             add(observer.observe_many(first, t_us[:1], energy=True), slice(0, 1), ntraj)
             overlaps(first, slice(0, 1), ntraj)
+            reduced = []  # per subsystem: the trajectory sums [T, dA, dA] on the device
+            if subsystems:
+                from .engine import reduced_density
+
+                for sub in subsystems:
+                    acc = torch.zeros((len(times), 2 ** len(sub), 2 ** len(sub)), dtype=torch.complex128,
+                                      device=observer.device)
+                    reduced_density(first, sub, out=acc[:1])
+                    acc[0] *= ntraj
+                    reduced.append(acc)
             del first
             done = 0
             jumps = []
@@ -1250,17 +1290,20 @@ class QutipEmulator:
                     ensemble_diag(snaps, diag[1:])
                     add(observer.observe_many(snaps, t_us[1:], energy=True), slice(1, None))
                     overlaps(snaps, slice(1, None))
+                    for sub, acc in zip(subsystems, reduced):
+                        reduced_density(snaps, sub, out=acc[1:])
                     jumps.append(eng.mc_jumps())
                     self.last_engine_stats = eng.stats()
                     del state, snaps
                 done += b
             host = diag.cpu().numpy()
-            del diag
+            reduced_host = [acc.cpu().numpy() for acc in reduced]
+            del diag, reduced
         finally:
             if own_observer:
                 observer.close()
         self.last_mc_jumps = np.concatenate(jumps)
-        return self._ensemble_results(sums.states(host, ntraj))
+        return self._ensemble_results(sums.states(host, ntraj, subsystems=subsystems, reduced_sums=reduced_host))
 
     def _ensemble_results(self, states: list[EnsembleState]) -> CoherentResults:
         """The results of an ensemble route: one ``StateResult`` per evaluation time around its ``EnsembleState``."""
@@ -1564,6 +1607,14 @@ class QutipEmulator:
         the diagonal ones.  Neither value is divided by ``norm2``.  Both options are used by the two ensemble routes
         alone and ignored by every other run; a wrong shape or a non-numeric entry raises ``ValueError`` before
         anything is solved.
+        ``mc_ensemble_subsystems``: site tuples such as ``[(0, 1), (3, 4, 5)]`` (positions in the register's qubit ids,
+        at most 6 each): the reduced density matrix ``mean_b Tr_rest |psi_b><psi_b|`` of each is reduced from the kets
+        (one ``reduced_density`` call per subsystem and chunk of trajectories into a ``[T, dA, dA]`` device
+        accumulator, read once at the end) - every expectation value of every operator supported on those atoms.
+        ``EnsembleState.ptrace``, ``results.reduced_states`` and ``results.entanglement_entropy`` serve these
+        subsystems and refuse any other.  Not divided by ``norm2``.  Used by the two-level ensemble route alone; an entry
+        that is no tuple of distinct sites in range, or one of more than 6 sites, raises ``ValueError`` before anything
+        is solved.
 
         ``general_jumps=True`` with ``mc_ensemble=True``: the same for the deterministic-noise run of the general
         path (multi-level bases, XY mode, a non-diagonal ``sum C^dag C``): the trajectories of ``general_jumps=True``
