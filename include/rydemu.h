@@ -363,7 +363,10 @@ int ryd_general_mc_solve_many(ryd_handle** hs, int32_t n, void* const* states_de
  * k_gen_apply_fused (round 6),
  * 524288 = ryd_general_observe on density matrices: 5 columns of rho per chunk (the chunked path without a 1-GiB state);
  * ryd_general_observe_many, ryd_general_observe_density_many: 5 evaluation times per chunk of tables (their chunked path
- * without 256 MiB of them).
+ * without 256 MiB of them),
+ * 1048576 = k_split_reg: the last run of a stretch, the double step of the step-size check behind it and its two regular
+ * sub-steps as segments of ONE launch (k_split_reg_seg).  The one bit that is ON in a handle this routine has never been
+ * called for: a call without it restores the launches of their own; the kets are bit for bit the same either way.
  * Never needed for results. */
 int ryd_set_path(ryd_handle* h, int32_t force_generic);
 

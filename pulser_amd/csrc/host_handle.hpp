@@ -74,7 +74,9 @@ struct ryd_handle {
   // work vectors
   cplx *wA = nullptr, *wB = nullptr, *kbuf = nullptr;
   cplx* wC = nullptr;              // second checkpoint buffer of the split-operator controller (allocated on first use; round 6)
-  double* split_err_pin = nullptr; // [B] pinned host copy of split_err (the one read-back of a check)
+  double* split_err_pin = nullptr; // [2][B] pinned host words of a check's result: the compare epilogue of k_split_reg writes them
+                                   // itself (split_err_pin_dev = their device address); k_split_diff's result is copied here
+  double* split_err_pin_dev = nullptr;
   // one-shot options of the next split_run on the register-resident kernel (run_split's check; consumed by the launch)
   cplx *fuse_dst = nullptr, *fuse_dst2 = nullptr;
   const cplx* fuse_cmp = nullptr;
@@ -111,6 +113,8 @@ struct ryd_handle {
   bool sched_for_split = false;   // the schedule being built is run by the split-operator path (host_sched.hpp: dev probe)
   bool snaps_outside = false;     // test / bench hook: every evaluation time closes a run of k_split_reg (round 4) instead of a
                                   // snapshot taken inside the run
+  bool no_check_segments = false; // test / bench hook: the step-size check of k_split_reg in launches of its own instead of
+                                  // as segments of the launch that ends the stretch before it (run_split)
   // ryd_set_snapshot_map: [B][snap_map_slots] ket offsets into ryd_solve's out_dev (device), or null (dense slots)
   long long* snap_map_dev = nullptr;
   int snap_map_slots = 0;

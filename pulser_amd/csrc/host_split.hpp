@@ -168,6 +168,8 @@ static int split_ensure_tables(ryd_handle* h, int n_stages) {
 }
 
 // Largest number of sub-steps whose coefficient tables stay under 32 MiB.
+// (A launch with segments - split_run_segments: a kept run of up to this many sub-steps and the three of the check behind it -
+// may go beyond it by those three: the table grows once, by a ninth at 256 x 14 atoms, and stays.)
 static int split_max_sub(const ryd_handle* h) {
   const size_t per_sub = (size_t)split_scheme(h).S * h->B * h->N * 4 * sizeof(double);
   return (int)std::min<size_t>(kSplitMaxSub, std::max<size_t>(1, ((size_t)32 << 20) / per_sub));
@@ -278,6 +280,29 @@ static int launch_split_reg(ryd_handle* h, const SplitArgs& A, const SplitRun& R
       hipLaunchKernelGGL((k_split_reg<14, 6, false>), dim3(1, h->B), dim3(256), lds, st, A, R, stride);
   } else
     hipLaunchKernelGGL((k_split_reg<N, 5, false>), dim3(1, h->B), dim3(NT), lds_x, st, A, R, stride);
+  HIPCHK(hipGetLastError());
+  return RYD_OK;
+}
+
+// the dev switch RYD_SPLIT_NR asks for another register shape than the segment kernel is built for
+static bool split_reg_plain_shape_forced() { return dev_env_int("RYD_SPLIT_NR", 0, 4, 6) != 0; }
+
+// k_split_reg_seg: the plain real-drive ket kernel over the segments of R, in the shape (and with the LDS) launch_split_reg
+// gives the plain kernel of that register size
+template <int N>
+static int launch_split_reg_seg(ryd_handle* h, const SplitArgs& A, const SplitRun& R, hipStream_t st) {
+  constexpr int NR = N == 12 ? 4 : 5;
+  constexpr int NT = 64 << (N - 6 - NR);
+  constexpr int CH = (1 << NR) / 4;
+  const size_t lds = (size_t)2 * NT * CH * 16 + SPLITR_TRIG * 16 + (size_t)(NT / 64) * splitr_gtab_slots<N, NR>(false, false, false, false) * 16 +
+                     (SPLIT_MAX_SUB * SPLIT_MAX_STAGES + 2) * 8 + (SPLITR_EMODE ? 4 * NT * 8 : 0) + (128 + 32) * 8;
+  const int dev = h->cfg.device;
+  static bool attr[64] = {};
+  if (lds > 64 * 1024 && (dev < 0 || dev >= 64 || !attr[dev])) {
+    HIPCHK(hipFuncSetAttribute((const void*)k_split_reg_seg<N, NR>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if (dev >= 0 && dev < 64) attr[dev] = true;
+  }
+  hipLaunchKernelGGL((k_split_reg_seg<N, NR>), dim3(1, h->B), dim3(NT), lds, st, A, R, (long long)h->B * N * 4);
   HIPCHK(hipGetLastError());
   return RYD_OK;
 }
@@ -411,7 +436,7 @@ static int split_run(ryd_handle* h, cplx* buf, const SubStep* subs, int nsub, hi
       A.dst = h->fuse_dst;
       A.dst2 = h->fuse_dst2;
       A.cmp = h->fuse_cmp;
-      A.cmp_err = h->split_err;
+      A.cmp_err = h->split_err_pin_dev;  // (run_split's pinned words: it reads them behind its synchronisation, no copy)
       h->fuse_dst = h->fuse_dst2 = nullptr;
       h->fuse_cmp = nullptr;
       h->fuse_done = true;
@@ -753,9 +778,124 @@ static int rows_split_pass(ryd_handle* h, cplx* buf, const std::vector<StepDesc>
   return RYD_OK;
 }
 
+// does sub-step s run the 4th-order 6-stage composition inside a run of the 6th-order scheme (split_advance)?
+static bool split_one_knot(const ryd_handle* h, const SubStep& s) { return h->split_s10 && !h->split_s6_only && s.alt != 0; }
+// does a run of plain kets take both compositions in one closed run of k_split_reg (SplitRun.mixed)?
+static bool split_mixes(const ryd_handle* h) { return split_reg_shape(h) && !h->mc && split_real(h) && !h->snaps_outside; }
+
+// The step-size check of run_split as ONE launch of k_split_reg_seg (SplitRun.nseg): the run that ends the stretch before the
+// check (`pend`, may be empty: kept back by split_advance), the wide step out of place into wA from the registers that run
+// has just stored, and the two regular sub-steps from the stored state, compared with wA on the way out and stored to the
+// state and to wC.  Every segment is a closed run with the records, weights and arithmetic of the launch it replaces: the
+// kets are bit for bit those of split_run(pend), split_run(wide -> wA), split_run(halves; cmp, dst2).
+// *done = false: nothing was launched (not the plain register-resident kernel: quantum jumps, complex-arithmetic kernel, a
+// drive beyond the tan-form bound, test hooks, too many sub-steps for one launch) - the caller takes those launches.
+static int split_run_segments(ryd_handle* h, cplx* state, const std::vector<SubStep>& pend, const SubStep& wide,
+                              const SubStep* halves, bool s6_check, hipStream_t st, bool* done) {
+  int rc;
+  *done = false;
+  static const bool seg_env = dev_env_flag("RYD_SPLIT_SEG", true);  // (dev A/B: RYD_DEV=1 RYD_SPLIT_SEG=0)
+  if (!seg_env || h->no_check_segments || !split_mixes(h) || split_reg_plain_shape_forced() || !h->wA || !h->wC || !h->split_err_pin_dev)
+    return RYD_OK;
+  split_plan(h);
+  const int N = h->N, B = h->B;
+  const int npend = (int)pend.size(), nsub = npend + 3;
+  if (nsub > SPLIT_MAX_SUB) return RYD_OK;
+  SubStep subs[SPLIT_MAX_SUB];
+  bool alt[SPLIT_MAX_SUB];
+  const bool s6_scheme = &split_scheme(h) == &kSplitS6;
+  bool any = false, all = true;
+  for (int s = 0; s < nsub; ++s) {
+    subs[s] = s < npend ? pend[s] : s == npend ? wide : halves[s - npend - 1];
+    alt[s] = s < npend ? split_one_knot(h, pend[s]) : s6_check;
+    any = any || alt[s];
+    all = all && alt[s];
+  }
+  // (uniform flags are no mixture, as in split_run: every sub-step still runs the composition its own launch would have run)
+  const bool mixed = any && !all && !s6_scheme;
+  const SplitScheme& sc = (all || s6_scheme) ? kSplitS6 : split_scheme(h);
+  const int nseg = npend > 0 ? 3 : 2;
+  int n_records = nseg;
+  for (int s = 0; s < nsub; ++s) n_records += (mixed && alt[s]) ? kSplitS6.S : sc.S;
+  if (n_records > SPLIT_MAX_SUB * SPLIT_MAX_STAGES + 2) return RYD_OK;  // (the kernel's table of stage weights)
+  {
+    // tan-form rotations need cos(beta |c|) away from zero (split_run): beyond the bound the launches go pass by pass
+    double bmax = 0.0;
+    for (int i = 0; i < sc.S; ++i) bmax = std::max(bmax, std::fabs(sc.b[i]));
+    if (mixed) for (int i = 0; i < kSplitS6.S; ++i) bmax = std::max(bmax, std::fabs(kSplitS6.b[i]));
+    for (int s = 0; s < nsub; ++s) {
+      const int span = std::max(1, (int)std::ceil((subs[s].u0 + subs[s].tau) / (h->tknots[subs[s].idx + 1] - h->tknots[subs[s].idx]) - 1e-9));
+      if (span_max(h->bd_c1, subs[s].idx, std::min(span, (int)h->bd_c1.size() - subs[s].idx)) * bmax * subs[s].tau > 1.0) return RYD_OK;
+    }
+  }
+  if ((rc = split_ensure_tables(h, n_records))) return rc;
+  SplitRun R;
+  std::memset(&R, 0, sizeof R);
+  for (int s = 0; s < SPLIT_MAX_SUB; ++s) R.snap[s] = -1;
+  R.nsub = nsub;
+  R.S = sc.S;
+  for (int i = 0; i <= sc.S; ++i) R.a[i] = sc.a[i];
+  for (int i = 0; i < sc.S; ++i) R.b[i] = sc.b[i];
+  if (mixed) {
+    R.mixed = 1;
+    R.S2 = kSplitS6.S;
+    for (int i = 0; i <= kSplitS6.S; ++i) R.a2[i] = kSplitS6.a[i];
+    for (int i = 0; i < kSplitS6.S; ++i) R.b2[i] = kSplitS6.b[i];
+    int at = 0;
+    for (int s = 0; s < nsub; ++s) {
+      R.alt[s] = alt[s] ? 1 : 0;
+      R.first[s] = (short)at;
+      at += alt[s] ? kSplitS6.S : sc.S;
+    }
+    R.first[nsub] = (short)at;
+  }
+  for (int s = 0; s < nsub; ++s) { R.idx[s] = subs[s].idx; R.u0[s] = subs[s].u0; R.tau[s] = subs[s].tau; }
+  R.tan_form = 1;
+  R.gauge = split_gauged(h) ? 1 : 0;
+  R.nseg = nseg;
+  int q = 0;
+  if (npend > 0) { R.seg_end[q] = npend; R.seg_flags[q] = 0; ++q; }
+  R.seg_end[q] = npend + 1;
+  R.seg_flags[q] = SPLIT_SEG_DST | (npend > 0 ? SPLIT_SEG_CONT : 0);  // the wide step: out of place into wA
+  ++q;
+  R.seg_end[q] = nsub;
+  R.seg_flags[q] = SPLIT_SEG_CMP;  // the regular sub-steps: in place, compared with wA, the new checkpoint into wC
+  const int total = B * N;
+  hipLaunchKernelGGL(k_split_coefs, dim3(h->dterms_dev ? (total + 3) / 4 : (total + 255) / 256, n_records), dim3(256), 0, st,
+                     h->pp_dev, h->n_knots - 1, h->desc_dev, h->dterms_dev, total, R, h->split_coefs);
+  HIPCHK(hipGetLastError());
+  SplitArgs A;
+  std::memset(&A, 0, sizeof A);
+  A.state = state;
+  A.e0 = h->e0_dev;
+  A.e0_stride = h->e0_mats == 1 ? 0 : ((long long)1 << N);
+  A.ccur = h->split_coefs;
+  A.N = N;
+  A.T = N;
+  A.dec_a = h->mc_a;
+  A.dec_b = h->mc_b;
+  A.dst = h->wA;
+  A.cmp = h->wA;
+  A.dst2 = h->wC;
+  A.cmp_err = h->split_err_pin_dev;
+  std::pair<hipEvent_t, hipEvent_t> ev1;
+  if (h->timing) { if ((rc = timing_begin(h, st, ev1))) return rc; }
+  rc = N == 14 ? launch_split_reg_seg<14>(h, A, R, st) : N == 13 ? launch_split_reg_seg<13>(h, A, R, st) : launch_split_reg_seg<12>(h, A, R, st);
+  if (rc) return rc;
+  if (h->timing) { HIPCHK(hipEventRecord(ev1.second, st)); h->ev_used.push_back(ev1); }
+  h->stats.n_launches++;
+  h->stats.n_applications += n_records - nseg;  // (n_stages - 1 of every closed segment)
+  h->stats.passes = 1;
+  *done = true;
+  return RYD_OK;
+}
+
 // Advance over any number of sub-steps (closed runs of at most split_max_sub).
+// `keep_last` (or null): where the last run is one of plain kets on the register-resident kernel and takes no snapshot, it is
+// not launched but handed back - run_split launches it together with the step-size check behind it (split_run_segments) or,
+// where no check follows, through this routine.
 static int split_advance(ryd_handle* h, cplx* buf, const std::vector<SubStep>& subs, hipStream_t st,
-                         const std::vector<int>* marks = nullptr, cplx* snaps = nullptr) {
+                         const std::vector<int>* marks = nullptr, cplx* snaps = nullptr, std::vector<SubStep>* keep_last = nullptr) {
   const int cap = split_max_sub(h);
   // Under the 6th-order scheme the stretches of ONE-KNOT sub-steps (the ~25 knots of spline ringing next to every
   // waveform kink, where nothing can be merged: 182 of the 547 schedule steps of the anneal) still run the 4th-order
@@ -764,10 +904,10 @@ static int split_advance(ryd_handle* h, cplx* buf, const std::vector<SubStep>& s
   // (the flag is set by run_split from the STEP a sub-step belongs to; until round 5 it was re-derived here from the
   // sub-step's own extent, which also caught the first of the 0.9-ns sub-steps of a 9-knot step - a 4th-order sub-step
   // where the controller had measured the 6th-order one: 8.7e-8 on a strongly interacting chain, tools/fuzz_ctrl.py seed 40)
-  auto one_knot = [&](const SubStep& s) { return h->split_s10 && !h->split_s6_only && s.alt != 0; };
+  auto one_knot = [&](const SubStep& s) { return split_one_knot(h, s); };
   size_t at = 0;
   // k_split_reg runs both compositions inside one closed run (SplitRun.mixed, round 5): the run is only cut at the cap
-  const bool mix = split_reg_shape(h) && !h->mc && split_real(h) && !h->snaps_outside;
+  const bool mix = split_mixes(h);
   std::vector<unsigned char> alt;
   if (mix) {
     alt.resize(subs.size());
@@ -777,6 +917,14 @@ static int split_advance(ryd_handle* h, cplx* buf, const std::vector<SubStep>& s
     const bool s6 = one_knot(subs[at]);
     size_t end = at + 1;
     while (end < subs.size() && end - at < (size_t)cap && (mix || one_knot(subs[end]) == s6)) ++end;
+    if (keep_last && mix && end == subs.size() && end - at + 3 <= (size_t)SPLIT_MAX_SUB) {
+      bool marked = false;
+      for (size_t q = at; q < end && marks && snaps; ++q) marked = marked || (*marks)[q] >= 0;
+      if (!marked) {
+        keep_last->assign(subs.begin() + at, subs.end());
+        return RYD_OK;
+      }
+    }
     // (a mixed run is a run of the handle's scheme whose flagged sub-steps take the other one: s6_run only without flags)
     int rc = split_run(h, buf, subs.data() + at, (int)(end - at), st, mix ? false : s6, marks ? marks->data() + at : nullptr,
                        snaps, mix ? alt.data() + at : nullptr);
@@ -1081,6 +1229,18 @@ static int run_split(ryd_handle* h, cplx* state, const std::vector<StepDesc>& sc
     for (size_t q = 0; q < sched.size(); ++q)
       if (kind_of(sched[q]) == 0) h_max[0] = std::max(h_max[0], std::min(glen[q], sub_cap_knots * knot_len(sched[q].idx)));
   }
+  // The run that ends a stretch is kept back (split_advance: keep_last) when nothing needs its state at once - no evaluation
+  // time, no quantum jumps: when the loop comes round to a check, the run, the wide step and the two regular sub-steps are
+  // segments of ONE launch (split_run_segments); otherwise it is launched as it would have been.  Which launch carries a
+  // sub-step changes nothing in its arithmetic, and every decision of the controller reads host state only.
+  std::vector<SubStep> pend;
+  const bool keep_runs = control && fuse_on && split_reg_shape(h) && !jumps && !h->no_check_segments;
+  auto flush_pending = [&]() -> int {
+    if (pend.empty()) return RYD_OK;
+    const int rcp = split_advance(h, state, pend, st);
+    pend.clear();
+    return rcp;
+  };
   while (i < sched.size()) {
     // A run of multi-knot steps that starts after knots which could not be removed (a waveform kink, the start of
     // the sequence) is a new regime: the local error measured before it says nothing about 8-knot sub-steps of the
@@ -1111,7 +1271,10 @@ static int run_split(ryd_handle* h, cplx* state, const std::vector<StepDesc>& sc
     // with an estimate of 1.8e-9.)
     const bool stale = !ctl[kd].known || new_regime || amp_grown;
     const bool probe_here = control && probe[kd] && off == 0.0 && ahead > tau_q(kd) * (1.0 + 1e-9);
-    if (control && (stale || probe_here || (informative && check_due(i, kd, ctl[kd].since)))) {
+    const bool take_check = control && (stale || probe_here || (informative && check_due(i, kd, ctl[kd].since)));
+    // (a run kept back at the end of the last stretch rides on the check's launch; no check here: it is launched as it was)
+    if (!take_check && (rc = flush_pending())) return rc;
+    if (take_check) {
       // ---- check: one sub-step whole (wA) against two halves (state) ----
       const StepDesc& d = sched[i];
       subs.clear();
@@ -1120,6 +1283,7 @@ static int run_split(ryd_handle* h, cplx* state, const std::vector<StepDesc>& sc
         // the first check of a call: its own start is the checkpoint (a sub-step never measured here - 8 knots of the
         // 6th-order scheme, say - may be far over its allowance, and the two halves kept below would carry 2^-p
         // of it: 3.8e-9 on a 14-atom slice before this)
+        if ((rc = flush_pending())) return rc;  // (the copy wants the state at the check's start)
         HIPCHK(hipMemcpyAsync(h->wB, state, bytes, hipMemcpyDeviceToDevice, st));
         ck_i = i;
         ck_off = off;
@@ -1137,7 +1301,12 @@ static int run_split(ryd_handle* h, cplx* state, const std::vector<StepDesc>& sc
       // unconsumed and the old sequence runs.
       const bool fuse_ok = fuse_on && split_reg_shape(h) && !jumps;
       if (fuse_ok && !h->wC) HIPCHK(hipMalloc((void**)&h->wC, bytes));
-      if (!h->split_err_pin) HIPCHK(hipHostMalloc((void**)&h->split_err_pin, (size_t)2 * h->B * sizeof(double)));
+      if (!h->split_err_pin) {
+        // (the compare epilogue of k_split_reg writes its two words per sequence straight into these: no device buffer and
+        // no copy between the launch and the synchronisation that reads them)
+        HIPCHK(hipHostMalloc((void**)&h->split_err_pin, (size_t)2 * h->B * sizeof(double)));
+        HIPCHK(hipHostGetDevicePointer((void**)&h->split_err_pin_dev, h->split_err_pin, 0));
+      }
       // DOUBLE-STEP check (round 6).  Where two sub-steps of the working length fit into what lies ahead on the same polynomial,
       // the scratch copy takes ONE step of 2 tau and the state its two regular sub-steps - which it would take anyway: the check
       // costs the 10 stages of the double step instead of 20 (whole + two halves against the 10 of the plain sub-step).  The
@@ -1147,6 +1316,16 @@ static int run_split(ryd_handle* h, cplx* state, const std::vector<StepDesc>& sc
       const double room = (kd == 0 ? glen[i] : sched[i].h) - off;
       const bool dbl = dbl_on && ctl[kd].known && ctl[kd].tau < 1e299 && room >= 2.0 * s0.tau * (1.0 - 1e-9);
       const SubStep wide = {s0.idx, s0.u0, (dbl ? 2.0 : 1.0) * s0.tau, kd};
+      const SubStep halves[2] = {{s0.idx, s0.u0, (dbl ? 1.0 : 0.5) * s0.tau, kd},
+                                 {s0.idx, s0.u0 + (dbl ? 1.0 : 0.5) * s0.tau, (dbl ? 1.0 : 0.5) * s0.tau, kd}};
+      // ONE launch for the run the last stretch kept back, the wide step and the two regular sub-steps (split_run_segments);
+      // where that is not to be had, the launches of their own that it stands for
+      bool seg_done = false;
+      if (fuse_ok && (rc = split_run_segments(h, state, pend, wide, halves, kd == 1, st, &seg_done))) return rc;
+      if (seg_done) pend.clear();
+      else if ((rc = flush_pending())) return rc;
+      bool fused2 = seg_done;
+      if (!seg_done) {
       h->fuse_done = false;
       if (fuse_ok) h->fuse_dst = h->wA;
       else HIPCHK(hipMemcpyAsync(h->wA, state, bytes, hipMemcpyDeviceToDevice, st));
@@ -1157,21 +1336,21 @@ static int run_split(ryd_handle* h, cplx* state, const std::vector<StepDesc>& sc
         if ((rc = split_run(h, h->wA, &wide, 1, st, kd == 1))) return rc;
       }
       const bool fused = fuse_ok && h->fuse_done;
-      const SubStep halves[2] = {{s0.idx, s0.u0, (dbl ? 1.0 : 0.5) * s0.tau, kd},
-                                 {s0.idx, s0.u0 + (dbl ? 1.0 : 0.5) * s0.tau, (dbl ? 1.0 : 0.5) * s0.tau, kd}};
       h->fuse_done = false;
       if (fused) { h->fuse_cmp = h->wA; h->fuse_dst2 = h->wC; }
       if ((rc = split_run(h, state, halves, 2, st, kd == 1))) return rc;
-      const bool fused2 = fused && h->fuse_done;
+      fused2 = fused && h->fuse_done;
       h->fuse_cmp = nullptr;
       h->fuse_dst2 = nullptr;
+      }
       if (!fused2) {
         HIPCHK(hipMemsetAsync(h->split_err, 0, (size_t)2 * h->B * sizeof(double), st));
         const unsigned nblk = (unsigned)std::min<size_t>(std::max<size_t>(h->dim >> 10, 1), 256);
         hipLaunchKernelGGL(k_split_diff, dim3(nblk, h->B), dim3(256), 0, st, state, h->wA, h->nb, h->split_err);
         HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h->split_err_pin, h->split_err, (size_t)2 * h->B * sizeof(double), hipMemcpyDeviceToHost, st));
       }
-      HIPCHK(hipMemcpyAsync(h->split_err_pin, h->split_err, (size_t)2 * h->B * sizeof(double), hipMemcpyDeviceToHost, st));
+      // (fused: the compare epilogue has written the pinned words itself)
       HIPCHK(hipStreamSynchronize(st));
       double e = 0.0, e_inf = 0.0, e_two = 0.0;
       for (int q = 0; q < h->B; ++q) {
@@ -1326,7 +1505,8 @@ static int run_split(ryd_handle* h, cplx* state, const std::vector<StepDesc>& sc
         // the evaluation time at the end of this step does not close the run (round 5): the snapshot is taken inside it
         marks.back() = d.snap;
       } else if (snap || jumps || j + 1 == stop) {
-        if ((rc = split_advance(h, state, subs, st, &marks, snaps))) return rc;
+        // (the end of the stretch, and nothing reads the state there: its last run waits for the check - see `pend`)
+        if ((rc = split_advance(h, state, subs, st, &marks, snaps, (keep_runs && !snap) ? &pend : nullptr))) return rc;
         subs.clear();
         marks.clear();
         if ((rc = finish_step(j))) return rc;
@@ -1334,6 +1514,7 @@ static int run_split(ryd_handle* h, cplx* state, const std::vector<StepDesc>& sc
       i = j + 1;
     }
   }
+  if ((rc = flush_pending())) return rc;
   if (control) {
     h->split_ctl[0] = ctl[0];
     h->split_ctl[1] = ctl[1];

@@ -786,6 +786,9 @@ extern "C" int ryd_set_path(ryd_handle* h, int32_t force_generic) {
     h->split_turns = (force_generic & 32768) != 0; // one-launch runs on the round-3 kernel (A/B)
     h->rows_ket = (force_generic & 65536) != 0;    // master-equation row passes on k_ket (A/B)
     h->snaps_outside = (force_generic & 131072) != 0;  // k_split_reg: a closed run per evaluation time (round 4, A/B)
+    // k_split_reg: a stretch and its step-size check as segments of one launch - what a handle does until this routine is
+    // called; a call WITHOUT the bit restores the launches of their own (A/B: Engine.set_path(check_segments=False))
+    h->no_check_segments = (force_generic & 1048576) == 0;
     {
       const bool s6 = (force_generic & 8192) != 0;  // split-operator passes: S6, sub-steps end at every knot
       if (s6 != h->split_s6_only) { h->split_s6_only = s6; h->split_known = false; }

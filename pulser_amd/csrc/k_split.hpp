@@ -34,10 +34,12 @@ __global__ __launch_bounds__(256) void k_split_coefs(const cplx* __restrict__ pp
   const int i = per_lane ? (int)(blockIdx.x * 256 + threadIdx.x) : (int)(blockIdx.x * 4 + (threadIdx.x >> 6));
   const int lane = per_lane ? 0 : (int)(threadIdx.x & 63);
   if (i >= total) return;
-  const int ns = R.nsub;
-  const int n_comp = splitrun_first(R, ns);  // stages of the compositions (mixed runs: not S ns)
   const bool pre_kick = R.kick_pre != 0.0 && blockIdx.y == 0;  // the extra stage 0: no D, rotation by kick_pre
-  const int j = (int)blockIdx.y - (R.kick_pre != 0.0 ? 1 : 0);
+  // the closed run the record belongs to: the whole of R, or one of its segments (SplitRun.nseg: their records lie one
+  // behind the other, each computed as if its sub-steps had been launched alone) - j = the record inside that run
+  const SplitSegView seg = splitrun_seg(R, splitrun_seg_of(R, (int)blockIdx.y));
+  const int n_comp = splitrun_seg_stages(R, seg);  // stages of the compositions (mixed runs: not S ns)
+  const int j = (int)blockIdx.y - seg.rec0 - (R.kick_pre != 0.0 ? 1 : 0);
   if (pre_kick) {
     if (lane == 0) {
       const ryd_qdesc d0 = desc[i];
@@ -65,10 +67,10 @@ __global__ __launch_bounds__(256) void k_split_coefs(const cplx* __restrict__ pp
   const bool closing = j >= n_comp;
   int s, st;
   if (closing) {
-    s = snap_close ? j - n_comp - 1 : ns - 1;
+    s = snap_close ? j - n_comp - 1 : seg.s1 - 1;
     st = splitrun_S(R, s);
   } else {
-    splitrun_locate(R, j, s, st);
+    splitrun_locate(R, seg, j, s, st);
   }
   const int S = splitrun_S(R, s);
   // D intervals: (knot interval, start offset, length)
@@ -79,7 +81,7 @@ __global__ __launch_bounds__(256) void k_split_coefs(const cplx* __restrict__ pp
   us_d[0] = R.u0[s] + cum * R.tau[s];
   len_d[0] = splitrun_a(R, s, st) * R.tau[s];
   us_d[1] = 0.0;
-  if (!closing && st == 0 && s > 0) {
+  if (!closing && st == 0 && s > seg.s0) {
     const double a_last = splitrun_a(R, s - 1, splitrun_S(R, s - 1));  // the previous sub-step's own composition
     idx_d[1] = R.idx[s - 1];
     us_d[1] = R.u0[s - 1] + (1.0 - a_last) * R.tau[s - 1];
@@ -137,7 +139,7 @@ __global__ __launch_bounds__(256) void k_split_coefs(const cplx* __restrict__ pp
       const double th_cur = closing ? 0.0 : theta(idx_c, u_c);
       // the rotation before this stage's D: the previous stage of the sub-step, the last one of the previous sub-step,
       // or none (the run starts in the laboratory frame)
-      const double th_prev = (st > 0) ? theta(R.idx[s], us_d[0]) : (s > 0 ? theta(idx_d[1], us_d[1]) : 0.0);
+      const double th_prev = (st > 0) ? theta(R.idx[s], us_d[0]) : (s > seg.s0 ? theta(idx_d[1], us_d[1]) : 0.0);
       dl += th_cur - th_prev;
     }
     if (R.tan_form == 1) gr = gi / C;  // (real drives: gr was 0; the host keeps |beta c| <= 1, so C >= 0.54)

@@ -291,9 +291,19 @@ __device__ __forceinline__ double splitr_partner(double v) {
 // registers - the OPEN state, see SplitArgs.snaps - are stored to the snapshot slot; k_split_snap_close finishes them.  A
 // front end that asks for the state at every knot (evaluation_times="Full", the reference's default, simulation.py:137)
 // or at every 10th used to close a run - a launch, a load and a store of the ket, a closing stage - per evaluation time.
-template <int N, int NR, bool DECAY, bool ROWS = false, bool CPLX = false, bool SNAP = false>
-__global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per_eu(1, NR >= 6 ? 1 : 2))) void k_split_reg(const SplitArgs A, const SplitRun R, long long stage_stride) {
+// SEG (k_split_reg_seg below; plain kets only): the run is a row of SEGMENTS (SplitRun.nseg, seg_end, seg_flags), each a
+// closed run of its own - load or keep the registers, stage loop, closing stage, the sinks of the controller's check - one
+// after another in ONE launch: a stretch, the double step of the step-size check behind it (out of place, from the registers
+// the stretch has just stored) and the two regular sub-steps the check compares it with.  The trig table, the stage weights
+// of all segments and the E0 pieces are set up once; the segment loop is the row loop of ROWS, and the stage body is the one
+// of the plain kernel.  The kernel without segments is a separate instantiation of the same body and does not change.
+template <int N, int NR, bool DECAY, bool ROWS, bool CPLX, bool SNAP, bool SEG>
+__device__ __forceinline__ void split_reg_body(const SplitArgs& A, const SplitRun& R, const long long stage_stride) {
   static_assert(!(SNAP && (ROWS || DECAY)), "snapshots inside a run: plain ket runs only");
+  static_assert(!(SEG && (ROWS || DECAY || CPLX || SNAP)), "segments: plain real-drive ket runs only");
+  // (the prefetch of the next stage's record starts at record 0 and flips the parity at every stage: it knows neither where a
+  // segment starts nor that the closing stage keeps the layout)
+  static_assert(!(SEG && SPLITR_PREF), "segments: SPLITR_PREF is not carried across segment boundaries");
   typedef SplitRegLayout<N, NR> L;
   constexpr int NW = L::NW, NTB = L::NTB, ND = L::ND;
   constexpr int NT = 64 << NW;
@@ -322,7 +332,8 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
   const unsigned tq = splitr_lane<ND>(t);  // the thread number by the index bits it holds (SPLITR_HM)
   const int b = ROWS ? (int)blockIdx.z : (int)blockIdx.y;
   const int n_pre = R.kick_pre != 0.0 ? 1 : 0;  // the opening kick is an extra stage 0 (no D)
-  const int n_stages = splitrun_first(R, R.nsub) + 1 + n_pre;
+  // (SEG: the records of all segments, a closing one each; no kicks there)
+  const int n_stages = SEG ? splitrun_records(R) : splitrun_first(R, R.nsub) + 1 + n_pre;
   // (SplitArgs.conj: conj(U) psi = conj(U conj(psi)) - the ket is conjugated at the load and at the store, the stages
   // in between are the ordinary ones: nothing in the stage loop knows about it)
   const double csgn = (ROWS && A.conj) ? -1.0 : 1.0;
@@ -332,8 +343,13 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
   if (SPLITR_WMODE) {
     // weight of E0 in the D of stage j: a_i tau (+ the last a tau carried over from the previous sub-step)
     for (int jj = (int)t; jj < n_stages; jj += NT) {
-      const int j = jj - n_pre;
-      wtab[jj] = j < 0 ? 0.0 : splitrun_weight(R, j);
+      if constexpr (SEG) {  // record jj of the launch = stage jj - rec0 of the segment it lies in
+        const SplitSegView g = splitrun_seg(R, splitrun_seg_of(R, jj));
+        wtab[jj] = splitrun_weight(R, g, jj - g.rec0);
+      } else {
+        const int j = jj - n_pre;
+        wtab[jj] = j < 0 ? 0.0 : splitrun_weight(R, j);
+      }
     }
   }
   for (unsigned k = t; k < SPLITR_TRIG; k += NT) {  // (before the state is loaded: the library routine wants registers)
@@ -411,21 +427,32 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
   cplx* __restrict__ const tslice = pbuf + 64 * w;
   const unsigned la = l & ((1u << ND) - 1u), lT = l >> ND;
 
-  for (unsigned row = ROWS ? blockIdx.y : 0u; row < (ROWS ? (1u << N) : 1u); row += ROWS ? gridDim.y : 1u) {
-  a_row = row;
+  double xr[NA], xi[NA];  // (outside the loop: a segment may go on from the registers of the one before it)
+  // (SEG: `row` counts the segments)
+  for (unsigned row = ROWS ? blockIdx.y : 0u; row < (ROWS ? (1u << N) : SEG ? (unsigned)R.nseg : 1u); row += ROWS ? gridDim.y : 1u) {
+  a_row = ROWS ? row : 0u;
   cplx* __restrict__ st = A.state + ((((size_t)b << (ROWS ? N : 0)) + (ROWS ? row : 0u)) << N);
   if (ROWS) __syncthreads();  // the previous row's readers of the factor table are done
   if (ROWS && A.use_pre && t < NA) ftl[128 + t] = row_factor(0, L::index(false, 0u, t), L::index(false, 0u, NA - 1));
   if (ROWS && A.use_pre) __syncthreads();
-  double xr[NA], xi[NA];
-  {
+  const SplitSegView seg = SEG ? splitrun_seg(R, (int)row) : SplitSegView{0, 0, 0};
+  const int seg_flags = SEG ? R.seg_flags[row] : 0;
+  // the segment before this one is done with the G tables (its compare reduces through them), and what it stored - the
+  // state a later segment loads, the buffer it compares with, by the same lanes at the same addresses - is complete
+  if (SEG && row > 0) __syncthreads();
+  if (!SEG || !(seg_flags & SPLIT_SEG_CONT)) {
     const double fl = (ROWS && A.use_pre) ? row_factor(0, L::index(false, tq, 0u), L::index(false, NT - 1, 0u)) : 1.0;
     // (SPLITR_XPASS: address = the lane's word XOR the named T bits, plus the pass bits)
-    const unsigned lw0 = kX ? L::index_x(false, tq, 0u) : 0u;
+    // (SEG: the lane's word is laundered through an empty asm, as for the snapshot stores below: the addresses are invariant
+    // in the segment loop, and hoisted out of it they are 64 more live registers over the stage loop - they spill, and every
+    // load of a segment then waits for the one before it)
+    unsigned lw0 = kX ? L::index_x(false, tq, 0u) : (SEG ? L::index(false, tq, 0u) : 0u);
+    if constexpr (SEG) asm volatile("" : "+v"(lw0));
     splitr_for<0, NA>([&](auto Rc) {
       constexpr int r = decltype(Rc)::value;
       cplx v;
       if constexpr (kX) v = st[L::addr_x(false, lw0, r)];
+      else if constexpr (SEG) v = st[lw0 + L::index(false, 0u, r)];
       else v = st[L::index(false, tq, r)];
       const double f = (ROWS && A.use_pre) ? fl * ftl[128 + r] : 1.0;
       xr[r] = v.x * f;
@@ -852,7 +879,10 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
         typedef const __attribute__((address_space(4))) unsigned* uptr_t;
         uptr_t nx = (uptr_t)na;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) wv[k] = nx[k < 7 ? 16 * k : 8 * N - 1];
+        // (one word per 64-byte line of the sequence's 8 N words, the last line by its last word - and never beyond it: at 12
+        // atoms the record is 6 lines, line 6 is the next sequence's, and behind the last sequence of the last record the end of
+        // the table - on a page boundary when the records are a multiple of 32, which a launch with segments can be)
+        for (int k = 0; k < 8; ++k) wv[k] = nx[(k < 7 && 16 * k < 8 * N) ? 16 * k : 8 * N - 1];
       } else {
         // lane k on line k (the last line by its last word); the value of the PREVIOUS stage's touch is folded first
         warm_va ^= warm_v;
@@ -860,7 +890,7 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
         // (the global address space by name: a generic pointer would make it a flat load, which counts on the LDS /
         // scalar counter as well)
         typedef const __attribute__((address_space(1))) unsigned* gptr_t;
-        warm_v = ((gptr_t)na)[k < 7u ? 16u * k : 8u * N - 1u];
+        warm_v = ((gptr_t)na)[(k < 7u && 16u * k < 8u * N) ? 16u * k : 8u * N - 1u];
       }
       __builtin_amdgcn_sched_barrier(0);
     };
@@ -1022,7 +1052,7 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
         typedef const __attribute__((address_space(4))) unsigned* uptr_t;
         uptr_t nx = (uptr_t)(unsigned long long)(coefs + (size_t)(sg + 1 < n_stages ? sg + 1 : sg) * stage_stride);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) warm ^= nx[k < 7 ? 16 * k : 8 * N - 1];
+        for (int k = 0; k < 8; ++k) warm ^= nx[(k < 7 && 16 * k < 8 * N) ? 16 * k : 8 * N - 1];
       }
       write_pre(C1{}, C2{});
       __syncthreads();
@@ -1058,7 +1088,13 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
     if constexpr (SPLITR_KWARM == 3) asm volatile("" ::"v"(warm_va));
   };
   const int n_full = R.kick_post == 0.0 ? n_stages - 1 : n_stages;
-  if constexpr (SNAP) {
+  if constexpr (SEG) {
+    // the records of this segment: its stages (an even number: it ends in the even layout, like every segment before
+    // it), then its own closing D
+    const int sg_close = seg.rec0 + splitrun_seg_stages(R, seg);
+    for (int sg = seg.rec0; sg < sg_close; ++sg) stage(sg, std::false_type{});
+    stage(sg_close, std::true_type{});
+  } else if constexpr (SNAP) {
     int snap_at = splitrun_first(R, 1) + n_pre - 1, snap_sub = 0;  // the stage that ends sub-step snap_sub
     for (int sg = 0; sg < n_full; ++sg) {
       stage(sg, std::false_type{});
@@ -1098,7 +1134,7 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
     for (int sg = 0; sg < n_full; ++sg) stage(sg, std::false_type{});
   }
   if (SPLITR_KWARM == 3) asm volatile("" ::"v"(warm_v));
-  if (n_full < n_stages) stage(n_stages - 1, std::true_type{});
+  if (!SEG && n_full < n_stages) stage(n_stages - 1, std::true_type{});
   // the layout is the odd one when an odd number of full stages ran
   // (tan form defers the product of a stage's cosines to the next stage's D; a run that closes on the kick has no next
   // stage, so the row is finished here: prod_k cos(kick c_k) = 1 - O(1e-18) for the default kick, 1e-13 per atom for
@@ -1119,14 +1155,19 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
   }
   bool stored = false;
   if constexpr (!ROWS) {
-    if (A.dst || A.dst2 || A.cmp) {
+    // (SEG: the sinks are chosen per segment)
+    cplx* const e_dst = (!SEG || (seg_flags & SPLIT_SEG_DST)) ? A.dst : nullptr;
+    cplx* const e_dst2 = (!SEG || (seg_flags & SPLIT_SEG_CMP)) ? A.dst2 : nullptr;
+    const cplx* const e_cmp = (!SEG || (seg_flags & SPLIT_SEG_CMP)) ? A.cmp : nullptr;
+    if (e_dst || e_dst2 || e_cmp) {
       // the controller's check (SplitArgs.dst / dst2 / cmp): out-of-place store, second store, comparison on the way out
       stored = true;
       const size_t boff = (size_t)b << N;
-      cplx* __restrict__ out = A.dst ? A.dst + boff : st;
-      cplx* __restrict__ out2 = A.dst2 ? A.dst2 + boff : nullptr;
-      const cplx* __restrict__ ref = A.cmp ? A.cmp + boff : nullptr;
-      const unsigned lw = kX ? (odd ? L::index_x(true, tq, 0u) : L::index_x(false, tq, 0u)) : (odd ? L::index(true, tq, 0u) : L::index(false, tq, 0u));
+      cplx* __restrict__ out = e_dst ? e_dst + boff : st;
+      cplx* __restrict__ out2 = e_dst2 ? e_dst2 + boff : nullptr;
+      const cplx* __restrict__ ref = e_cmp ? e_cmp + boff : nullptr;
+      unsigned lw = kX ? (odd ? L::index_x(true, tq, 0u) : L::index_x(false, tq, 0u)) : (odd ? L::index(true, tq, 0u) : L::index(false, tq, 0u));
+      if constexpr (SEG) asm volatile("" : "+v"(lw));  // (not hoisted out of the segment loop: see the load)
       double dmax = 0.0, dsum = 0.0;
       auto put = [&](unsigned ix, double vx, double vy) {
         const cplx v = make_double2(vx, vy);
@@ -1164,7 +1205,17 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
       }
     }
   }
-  if (!stored) {
+  if (SEG && !stored) {
+    // (the same store with the addresses formed here, from the laundered word of the lane)
+    unsigned lw = kX ? (odd ? L::index_x(true, tq, 0u) : L::index_x(false, tq, 0u)) : (odd ? L::index(true, tq, 0u) : L::index(false, tq, 0u));
+    asm volatile("" : "+v"(lw));
+    if (odd) {
+      splitr_for<0, NA>([&](auto Rc) { constexpr int r = decltype(Rc)::value; st[kX ? L::addr_x(true, lw, r) : lw + L::index(true, 0u, r)] = make_double2(xr[r], xi[r]); });
+    } else {
+      splitr_for<0, NA>([&](auto Rc) { constexpr int r = decltype(Rc)::value; st[kX ? L::addr_x(false, lw, r) : lw + L::index(false, 0u, r)] = make_double2(xr[r], xi[r]); });
+    }
+  }
+  if (!SEG && !stored) {
   splitr_for<0, NA>([&](auto Rc) {
     constexpr int r = decltype(Rc)::value;
     const double f = (ROWS && A.use_post) ? fl * ftl[128 + r] : 1.0;
@@ -1173,4 +1224,17 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
   });
   }
   }  // rows
+}
+
+template <int N, int NR, bool DECAY, bool ROWS = false, bool CPLX = false, bool SNAP = false>
+__global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per_eu(1, NR >= 6 ? 1 : 2))) void k_split_reg(const SplitArgs A, const SplitRun R, long long stage_stride) {
+  split_reg_body<N, NR, DECAY, ROWS, CPLX, SNAP, false>(A, R, stage_stride);
+}
+
+// the plain real-drive ket kernel over the segments of R (R.nseg >= 1): same launch shape and LDS as k_split_reg<N, NR, false>
+// (two waves per SIMD asked for, not merely allowed: with the load and the sinks inside the segment loop the allocator
+// otherwise takes more than 256 vector registers at 12 and 13 atoms, and a CU holds one workgroup where the plain kernel has two)
+template <int N, int NR>
+__global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_split_reg_seg(const SplitArgs A, const SplitRun R, long long stage_stride) {
+  split_reg_body<N, NR, false, false, false, false, true>(A, R, stage_stride);
 }

@@ -20,6 +20,14 @@
 #define SPLITR_INSTANCES_13(X) SPLITR_INSTANCES_OF(13, X)
 #define SPLITR_INSTANCES_14(X) SPLITR_INSTANCES_OF(14, X) X(14, 6, false, false, false, false)
 
+// k_split_reg_seg<N, NR>: the plain ket kernel over the segments of a run (a stretch and its step-size check in one launch) -
+// the shapes launch_split_reg takes for plain real-drive kets
+#define SPLITR_SEG_INSTANCES_12(X) X(12, 4)
+#define SPLITR_SEG_INSTANCES_13(X) X(13, 5)
+#define SPLITR_SEG_INSTANCES_14(X) X(14, 5)
+#define SPLITR_SEG_EXTERN(N_, NR_) extern template __global__ void k_split_reg_seg<N_, NR_>(const SplitArgs, const SplitRun, long long);
+#define SPLITR_SEG_DEFINE(N_, NR_) template __global__ void k_split_reg_seg<N_, NR_>(const SplitArgs, const SplitRun, long long);
+
 #define SPLITR_EXTERN(N_, NR_, D_, R_, C_, S_) \
   extern template __global__ void k_split_reg<N_, NR_, D_, R_, C_, S_>(const SplitArgs, const SplitRun, long long);
 #define SPLITR_DEFINE(N_, NR_, D_, R_, C_, S_) \

@@ -68,6 +68,9 @@ typedef double2 cplx;
 SPLITR_INSTANCES_12(SPLITR_EXTERN)
 SPLITR_INSTANCES_13(SPLITR_EXTERN)
 SPLITR_INSTANCES_14(SPLITR_EXTERN)
+SPLITR_SEG_INSTANCES_12(SPLITR_SEG_EXTERN)
+SPLITR_SEG_INSTANCES_13(SPLITR_SEG_EXTERN)
+SPLITR_SEG_INSTANCES_14(SPLITR_SEG_EXTERN)
 #endif
 #include "k_observe.hpp"
 #include "k_gen_observe.hpp"

@@ -61,6 +61,11 @@ struct SplitArgs {
 // carries the last D(a_7) of sub-step s - 1); stage 6 nsub only closes with D(a_7).
 #define SPLIT_MAX_SUB 64
 #define SPLIT_MAX_STAGES 10
+#define SPLIT_MAX_SEG 3
+// flags of a segment (SplitRun.seg_flags): where its ket comes from and where it goes
+#define SPLIT_SEG_CONT 1  /* the registers of the segment before it (which stored them to SplitArgs.state) instead of a load */
+#define SPLIT_SEG_DST 2   /* stored to SplitArgs.dst instead of SplitArgs.state */
+#define SPLIT_SEG_CMP 4   /* compared with SplitArgs.cmp on the way out (cmp_err) and also stored to SplitArgs.dst2 */
 struct SplitRun {
   int nsub;
   int S;  // stages of the composition: 6 (4th order, Blanes & Moan S6) or 10 (6th order, S10)
@@ -95,19 +100,27 @@ struct SplitRun {
   double b2[SPLIT_MAX_STAGES];
   unsigned char alt[SPLIT_MAX_SUB];
   short first[SPLIT_MAX_SUB + 1];
+  // SEGMENTS (k_split_coefs, k_split_reg_seg: a stretch and the step-size check behind it in one launch).  nseg == 0: the
+  // sub-steps are ONE closed run, as above.  nseg = 1 .. 3: segment q holds the sub-steps seg_end[q - 1] (0 for q = 0) up to
+  // seg_end[q] - 1 and is a closed run of its own - its first stage carries no D of the sub-step before it, it ends with its
+  // own closing stage, and its records are those of the same sub-steps launched alone.  The records of the segments lie one
+  // behind the other: segment q starts at record splitrun_first(R, its first sub-step) + q.  seg_flags[q]: SPLIT_SEG_*.
+  int nseg;
+  int seg_end[SPLIT_MAX_SEG];
+  int seg_flags[SPLIT_MAX_SEG];
 };
 
 // the composition of sub-step s / the stage layout of a run (every kernel and the host go through these)
-__host__ __device__ __forceinline__ int splitrun_S(const SplitRun& R, int s) { return (R.mixed && R.alt[s]) ? R.S2 : R.S; }
-__host__ __device__ __forceinline__ double splitrun_a(const SplitRun& R, int s, int i) {
+__host__ __device__ __forceinline__ constexpr int splitrun_S(const SplitRun& R, int s) { return (R.mixed && R.alt[s]) ? R.S2 : R.S; }
+__host__ __device__ __forceinline__ constexpr double splitrun_a(const SplitRun& R, int s, int i) {
   return (R.mixed && R.alt[s]) ? R.a2[i] : R.a[i];
 }
-__host__ __device__ __forceinline__ double splitrun_b(const SplitRun& R, int s, int i) {
+__host__ __device__ __forceinline__ constexpr double splitrun_b(const SplitRun& R, int s, int i) {
   return (R.mixed && R.alt[s]) ? R.b2[i] : R.b[i];
 }
-__host__ __device__ __forceinline__ int splitrun_first(const SplitRun& R, int s) { return R.mixed ? (int)R.first[s] : R.S * s; }
+__host__ __device__ __forceinline__ constexpr int splitrun_first(const SplitRun& R, int s) { return R.mixed ? (int)R.first[s] : R.S * s; }
 // stage j of the compositions (0 <= j < splitrun_first(R, nsub)) -> (sub-step, stage inside it)
-__host__ __device__ __forceinline__ void splitrun_locate(const SplitRun& R, int j, int& s, int& st) {
+__host__ __device__ __forceinline__ constexpr void splitrun_locate(const SplitRun& R, int j, int& s, int& st) {
   if (!R.mixed) {
     s = j / R.S;
     st = j % R.S;
@@ -121,17 +134,110 @@ __host__ __device__ __forceinline__ void splitrun_locate(const SplitRun& R, int 
   s = lo;
   st = j - (int)R.first[lo];
 }
-// weight of E0 in the D of composition stage j (the last D of the previous sub-step rides on a sub-step's first stage);
-// j == splitrun_first(R, nsub): the closing D
-__host__ __device__ __forceinline__ double splitrun_weight(const SplitRun& R, int j) {
-  const int total = splitrun_first(R, R.nsub);
-  if (j >= total) return splitrun_a(R, R.nsub - 1, splitrun_S(R, R.nsub - 1)) * R.tau[R.nsub - 1];
-  int s, st;
-  splitrun_locate(R, j, s, st);
+// A closed run inside R: the sub-steps s0 .. s1 - 1; its records start at rec0, the closing one is rec0 + its stages.
+// The whole of R when it has no segments.
+struct SplitSegView {
+  int s0, s1, rec0;
+};
+__host__ __device__ __forceinline__ constexpr int splitrun_nseg(const SplitRun& R) { return R.nseg > 0 ? R.nseg : 1; }
+__host__ __device__ __forceinline__ constexpr SplitSegView splitrun_seg(const SplitRun& R, int q) {
+  if (R.nseg <= 0) return {0, R.nsub, 0};
+  const int s0 = q > 0 ? R.seg_end[q - 1] : 0;
+  return {s0, R.seg_end[q], splitrun_first(R, s0) + q};
+}
+// stages of the compositions of a segment (its closing record follows them) / records of the whole launch
+__host__ __device__ __forceinline__ constexpr int splitrun_seg_stages(const SplitRun& R, const SplitSegView& g) {
+  return splitrun_first(R, g.s1) - splitrun_first(R, g.s0);
+}
+__host__ __device__ __forceinline__ constexpr int splitrun_records(const SplitRun& R) { return splitrun_first(R, R.nsub) + splitrun_nseg(R); }
+// the segment a record belongs to
+__host__ __device__ __forceinline__ constexpr int splitrun_seg_of(const SplitRun& R, int rec) {
+  int q = 0;
+  while (q + 1 < R.nseg && rec >= splitrun_first(R, R.seg_end[q]) + q + 1) ++q;
+  return q;
+}
+// stage jl of segment g (0 <= jl < splitrun_seg_stages) -> (sub-step, stage inside it)
+__host__ __device__ __forceinline__ constexpr void splitrun_locate(const SplitRun& R, const SplitSegView& g, int jl, int& s, int& st) {
+  splitrun_locate(R, splitrun_first(R, g.s0) + jl, s, st);
+}
+// weight of E0 in the D of stage jl of the closed run g (the last D of the previous sub-step OF THE RUN rides on a
+// sub-step's first stage); jl == splitrun_seg_stages(R, g): the closing D
+__host__ __device__ __forceinline__ constexpr double splitrun_weight(const SplitRun& R, const SplitSegView& g, int jl) {
+  const int total = splitrun_seg_stages(R, g);
+  if (jl >= total) return splitrun_a(R, g.s1 - 1, splitrun_S(R, g.s1 - 1)) * R.tau[g.s1 - 1];
+  int s = 0, st = 0;
+  splitrun_locate(R, g, jl, s, st);
   double w = splitrun_a(R, s, st) * R.tau[s];
-  if (st == 0 && s > 0) w += splitrun_a(R, s - 1, splitrun_S(R, s - 1)) * R.tau[s - 1];
+  if (st == 0 && s > g.s0) w += splitrun_a(R, s - 1, splitrun_S(R, s - 1)) * R.tau[s - 1];
   return w;
 }
+// ... of a run without segments, by its stage j (j == splitrun_first(R, nsub): the closing D)
+__host__ __device__ __forceinline__ constexpr double splitrun_weight(const SplitRun& R, int j) {
+  return splitrun_weight(R, SplitSegView{0, R.nsub, 0}, j);
+}
+
+// Compile-time self-check of the segment view: a mixed run of seven sub-steps cut into three segments (4 + 1 + 2, the
+// shape of a stretch, a double step and its two regular sub-steps).  Every segment must number its stages, place its
+// records and weigh its D factors exactly like the same sub-steps described as a run of their own.
+constexpr bool splitrun_segments_ok() {
+  constexpr int NS = 7;
+  constexpr int ends[SPLIT_MAX_SEG] = {4, 5, 7};
+  constexpr unsigned char alts[NS] = {0, 1, 1, 0, 0, 1, 0};
+  SplitRun R{};
+  R.nsub = NS;
+  R.S = 10;
+  R.S2 = 6;
+  R.mixed = 1;
+  for (int i = 0; i <= 10; ++i) R.a[i] = 0.01 * (i + 3);
+  for (int i = 0; i <= 6; ++i) R.a2[i] = 0.07 * (i + 1);
+  int at = 0;
+  for (int s = 0; s < NS; ++s) {
+    R.alt[s] = alts[s];
+    R.tau[s] = 1e-3 * (2 * s + 1);
+    R.first[s] = (short)at;
+    at += alts[s] ? 6 : 10;
+  }
+  R.first[NS] = (short)at;
+  R.nseg = 3;
+  for (int q = 0; q < 3; ++q) R.seg_end[q] = ends[q];
+  if (splitrun_records(R) != at + 3) return false;
+  int rec = 0;
+  for (int q = 0; q < 3; ++q) {
+    const SplitSegView g = splitrun_seg(R, q);
+    SplitRun Q{};  // the sub-steps of segment q as a run of their own
+    Q.nsub = g.s1 - g.s0;
+    Q.S = R.S;
+    Q.S2 = R.S2;
+    Q.mixed = 1;
+    for (int i = 0; i <= 10; ++i) Q.a[i] = R.a[i];
+    for (int i = 0; i <= 6; ++i) Q.a2[i] = R.a2[i];
+    int qa = 0;
+    for (int s = 0; s < Q.nsub; ++s) {
+      Q.alt[s] = R.alt[g.s0 + s];
+      Q.tau[s] = R.tau[g.s0 + s];
+      Q.first[s] = (short)qa;
+      qa += Q.alt[s] ? 6 : 10;
+    }
+    Q.first[Q.nsub] = (short)qa;
+    if (g.rec0 != rec || splitrun_seg_stages(R, g) != qa) return false;
+    for (int jl = 0; jl <= qa; ++jl) {
+      if (splitrun_seg_of(R, rec + jl) != q) return false;
+      if (splitrun_weight(R, g, jl) != splitrun_weight(Q, jl)) return false;
+      if (jl == qa) break;
+      int s = 0, st = 0, s2 = 0, st2 = 0;
+      splitrun_locate(R, g, jl, s, st);
+      splitrun_locate(Q, jl, s2, st2);
+      if (s - g.s0 != s2 || st != st2) return false;
+    }
+    rec += qa + 1;
+  }
+  // without segments the view is the run itself
+  SplitRun P = R;
+  P.nseg = 0;
+  const SplitSegView w = splitrun_seg(P, 0);
+  return w.s0 == 0 && w.s1 == NS && w.rec0 == 0 && splitrun_records(P) == at + 1 && splitrun_seg_of(P, at) == 0;
+}
+static_assert(splitrun_segments_ok(), "SplitRun segments: each must equal the same sub-steps as a run of their own");
 
 struct SplitSnapList {
   int n;
