@@ -661,6 +661,39 @@ int ryd_reduced_density(const void* states_dev, int32_t n_times, int32_t n_batch
                         int32_t n_split, void* scratch_dev, int64_t scratch_bytes,
                         int32_t device, void* stream);
 
+/* Replaces: Qobj.ptrace(sel) on the density matrices mesolve returns (the states QutipEmulator.run hands out for a
+ * noisy run, pulser_simulation/simulation.py:739-748), for matrices that are still on the device - the reduced density
+ * matrix rho_A = Tr_rest rho of a small set A of atoms (subsystem purity under dephasing, the entropy a noise channel
+ * adds, every expectation value supported on A), summed over a trajectory axis:
+ *   out[i][a][a'] += sum_b sum_r rho(i, b)[idx(a, r)][idx(a', r)]     i < n_times, b < n_batch.
+ * Only dA * dim of the dim^2 elements of a matrix are read.
+ * dim = local_dim^n_sites, local_dim in 2..4; atom 0 is the most significant digit (stride local_dim^(n_sites-1-k)).
+ * keep: HOST int32[n_keep], strictly ascending site indices, read before the launch; dA = local_dim^n_keep <= 64 (six
+ * qubits, three qutrits, three four-level atoms).  Row a is the base-local_dim number of the kept digits in ascending
+ * site order (the first kept site is the most significant); r runs over the configurations of the other sites.
+ * n_keep = n_sites is valid: the rest is empty and the result is the sum over b of the matrices themselves.
+ * matrix (i, b) is row-major, contiguous over dim * dim, and starts at states_dev + i*stride_t + b*stride_b (complex128
+ * elements, 64-bit offsets; both strides >= dim*dim).  out_dev complex128[n_times][dA][dA], row-major and contiguous,
+ * is ACCUMULATED into: zero it once, then call once per chunk of trajectories.
+ * No Hermitian assumption: every one of the dA^2 entries is the sum of the stored elements named above - nothing is
+ * mirrored or conjugated, both triangles of rho are read, and nothing is divided by a trace.
+ * n_split workgroups share one time by dividing the r range: 1 needs no scratch; > 1 writes partials
+ * complex128[n_times][n_split][dA][dA] to scratch_dev (scratch_bytes must hold them, else RYD_ERR_INVALID - never a
+ * silent other split) and a second launch adds them onto out in the order 0 .. n_split-1; 0 lets the library choose
+ * from n_times, dim, keep and the scratch given (none: 1).  No atomics: the summation order is a function of (dim, keep,
+ * n_batch, n_split) alone, and two calls on the same input with the same n_split are bitwise equal.  Times beyond
+ * 65 535 are walked with a grid stride.
+ * n_times = 0 returns RYD_OK and launches nothing.  Null states_dev / out_dev / keep, negative counts, n_batch < 1,
+ * dim != local_dim^n_sites, dim >= 2^31, a stride below dim*dim, keep out of range or not strictly ascending, dA > 64:
+ * RYD_ERR_INVALID, decided before the device is touched.  No handle, no host synchronisation. */
+int ryd_reduced_density_dm(const void* states_dev, int32_t n_times, int32_t n_batch,
+                           int64_t stride_t, int64_t stride_b, int64_t dim,
+                           int32_t local_dim, int32_t n_sites,
+                           const int32_t* keep /* HOST int32[n_keep], strictly ascending */, int32_t n_keep,
+                           void* out_dev /* complex128[n_times][dA][dA] */,
+                           int32_t n_split, void* scratch_dev, int64_t scratch_bytes,
+                           int32_t device, void* stream);
+
 int ryd_get_stats(const ryd_handle* h, ryd_stats* out);
 int ryd_reset_stats(ryd_handle* h);
 

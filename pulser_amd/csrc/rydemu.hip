@@ -89,4 +89,5 @@ SPLITR_SEG_INSTANCES_14(SPLITR_SEG_EXTERN)
 #include "host_observables.hpp"
 #include "k_ensemble.hpp"
 #include "k_ptrace.hpp"
+#include "k_ptrace_dm.hpp"
 #include "host_replay.hpp"

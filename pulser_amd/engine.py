@@ -137,7 +137,8 @@ def ensemble_diag(states: Any, diag: Any) -> None:
         torch.cuda.current_stream(states.device).cuda_stream))
 
 
-REDUCED_DENSITY_MAX_ROWS = 64  # dA of ryd_reduced_density at most: six qubits, three qutrits, three four-level atoms
+# dA of ryd_reduced_density and ryd_reduced_density_dm at most: six qubits, three qutrits, three four-level atoms
+REDUCED_DENSITY_MAX_ROWS = 64
 
 
 def check_keep(keep: Any, n_sites: int) -> tuple[int, ...]:
@@ -240,6 +241,100 @@ def reduced_density(states: Any, keep: Any, local_dim: int = 2, out: Any = None,
         scratch = torch.empty((n_t, parts, d_a, d_a), dtype=torch.complex128, device=states.device)
     keep_arr = np.ascontiguousarray(sites, dtype=np.int32)
     _lib.check(_lib.load().ryd_reduced_density(
+        states.data_ptr(), n_t, n_b, stride_t, stride_b, dim, local_dim, n_sites, keep_arr.ctypes.data, len(sites),
+        out.data_ptr(), n_split, None if scratch is None else scratch.data_ptr(),
+        0 if scratch is None else scratch.numel() * 16, int(states.device.index or 0),
+        torch.cuda.current_stream(states.device).cuda_stream))
+    return out
+
+
+def reduced_density_dm_splits(n_times: int, dim: int, d_a: int, local_dim: int = 2) -> int:
+    """The most workgroups per time ``ryd_reduced_density_dm`` takes when it chooses (``n_split = 0``), given the
+    scratch for them - the library's own rule: ``min(1024 // T, steps // 8)``, at least 1, where a workgroup walks
+    ``steps = R / NS`` steps per matrix, ``R = D / dA`` and ``NS`` the largest power of ``local_dim`` with
+    ``NS * dA^2 <= 256`` (at most ``R``); from ``dA^2 > 256`` on ``NS = 1`` and the rule is ``steps // 4``."""
+    rest = dim // d_a
+    slots, per_split = 1, 4
+    if d_a * d_a <= 256:
+        per_split = 8
+        while slots * local_dim <= rest and d_a * d_a * slots * local_dim <= 256:
+            slots *= local_dim
+    return max(1, min(1024 // max(n_times, 1), rest // slots // per_split))
+
+
+def reduced_density_dm(states: Any, keep: Any, local_dim: int = 2, out: Any = None, n_split: int = 0) -> Any:
+    """``out[t, a, a'] += sum_b sum_r rho(t, b)[idx(a, r), idx(a', r)]`` on the device (``ryd_reduced_density_dm``):
+    the partial trace ``Tr_rest rho`` of every density matrix over the sites ``keep``, summed over axis 1 - what
+    ``Qobj.ptrace(keep)`` gives for the matrices of a master-equation run, without a matrix leaving the device.  Only
+    ``dA * D`` of the ``D * D`` elements of a matrix are read.
+
+    ``states`` is a complex128 CUDA tensor ``[T, B >= 1, D, D]`` with ``D = local_dim**n`` (``local_dim`` 2, 3 or 4), or
+    a view of one whose last two axes are contiguous (the strides of the first two axes are passed on).  Sites, ``keep``
+    and the row order are those of ``reduced_density``; ``dA = local_dim**len(keep)`` is at most 64, and keeping every
+    site is valid.  Nothing is assumed Hermitian: every entry is the sum of the stored elements the formula names,
+    nothing is mirrored, conjugated or divided by a trace.
+
+    Returns ``out``, complex128 ``[T, dA, dA]`` contiguous on the same device: a new zero tensor when none is given,
+    else the one given, which is ACCUMULATED into.  ``n_split`` workgroups share one time: 1 is one workgroup per time,
+    0 lets the library choose.  A scratch tensor is allocated only when a split is used: ``T * n_split * dA * dA``
+    complex128 for a given ``n_split > 1``, and for ``n_split = 0`` the ``reduced_density_dm_splits(T, D, dA, local_dim)``
+    partials per time the library can use (none when that is 1: one workgroup per time).  No atomics: repeated
+    calls with the same ``n_split`` give bitwise equal results."""
+    import torch
+
+    # (what can be said of a tensor wherever it lives is said first: the checks below need no device)
+    if not isinstance(states, torch.Tensor):
+        raise ValueError("states must be a CUDA tensor")
+    if states.dtype != torch.complex128:
+        raise TypeError(f"a complex128 states tensor expected, got {states.dtype}")
+    if states.dim() != 4 or int(states.shape[1]) < 1 or int(states.shape[2]) < 1 or states.shape[2] != states.shape[3]:
+        raise ValueError(f"shape {tuple(states.shape)} does not match [T, B >= 1, D, D]")
+    n_t, n_b, dim = (int(v) for v in states.shape[:3])
+    if int(local_dim) not in (2, 3, 4):
+        raise ValueError(f"local_dim must be 2, 3 or 4, got {local_dim}")
+    local_dim = int(local_dim)
+    n_sites = sites_of_dim(dim, local_dim)
+    sites = check_keep(keep, n_sites)
+    d_a = local_dim ** len(sites)
+    if d_a > REDUCED_DENSITY_MAX_ROWS:
+        raise ValueError(f"{len(sites)} sites of local dimension {local_dim} make a {d_a} x {d_a} matrix: the device "
+                         f"partial trace serves at most {REDUCED_DENSITY_MAX_ROWS} rows")
+    if n_t > 0 and ((states.stride(3) != 1 and dim > 1) or states.stride(2) != dim):
+        raise ValueError("the last two axes of states must be contiguous (the first two may be strided)")
+    n_split = int(n_split)
+    if n_split < 0:
+        raise ValueError(f"n_split must be 0 (the library's choice) or positive, got {n_split}")
+    if not states.is_cuda:
+        raise ValueError("states must be a CUDA tensor")
+    _torch()
+    if out is None:
+        out = torch.zeros((n_t, d_a, d_a), dtype=torch.complex128, device=states.device)
+    else:
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == states.device):
+            raise ValueError("states and out must be CUDA tensors on the same device")
+        if out.dtype != torch.complex128:
+            raise TypeError(f"a complex128 out tensor expected, got {out.dtype}")
+        if tuple(out.shape) != (n_t, d_a, d_a):
+            raise ValueError(f"out has the shape {tuple(out.shape)}, expected {(n_t, d_a, d_a)}")
+        if not out.is_contiguous():
+            raise ValueError("a contiguous out tensor expected")
+    if n_t == 0:
+        return out
+    # (the stride of an axis of length 1 is arbitrary in torch and never used: any valid value will do)
+    stride_b = int(states.stride(1)) if n_b > 1 else dim * dim
+    stride_t = int(states.stride(0)) if n_t > 1 else max(n_b * stride_b, dim * dim)
+    if stride_b < dim * dim or stride_t < dim * dim:
+        raise ValueError(f"strides {stride_t} / {stride_b} of the first two axes are smaller than a matrix ({dim * dim})")
+    parts = n_split
+    if n_split == 0:
+        parts = reduced_density_dm_splits(n_t, dim, d_a, local_dim)
+        if parts < 2:
+            n_split, parts = 1, 1
+    scratch = None
+    if parts > 1:
+        scratch = torch.empty((n_t, parts, d_a, d_a), dtype=torch.complex128, device=states.device)
+    keep_arr = np.ascontiguousarray(sites, dtype=np.int32)
+    _lib.check(_lib.load().ryd_reduced_density_dm(
         states.data_ptr(), n_t, n_b, stride_t, stride_b, dim, local_dim, n_sites, keep_arr.ctypes.data, len(sites),
         out.data_ptr(), n_split, None if scratch is None else scratch.data_ptr(),
         0 if scratch is None else scratch.numel() * 16, int(states.device.index or 0),

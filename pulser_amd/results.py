@@ -194,11 +194,20 @@ class DeviceState:
         return QState(self.full()).overlap(other)
 
     def ptrace(self, keep: Any, local_dim: int = 2) -> "QState":
-        """``QState.ptrace`` of this state.  The ket form is traced as a ket (the matrix is not expanded); a density
-        matrix on the device is copied to the host first: the device partial trace serves kets only."""
+        """``QState.ptrace`` of this state.  The ket form is traced as a ket (the matrix is not expanded).  A density
+        matrix on a GPU is traced there (``engine.reduced_density_dm``, at most 64 rows): only the ``dA x dA`` matrix
+        crosses PCIe.  A larger subsystem copies the whole matrix to the host first (``full()``)."""
         if self._ket is not None:
             return QState(_ptrace_host(self._ket.reshape(-1, 1), True, keep, int(local_dim)))
-        return QState(_ptrace_host(self.full(), False, keep, int(local_dim)))
+        t, d = self._tensor, int(local_dim)
+        if _is_gpu_tensor(t) and t.is_contiguous() and d in (2, 3, 4):
+            from .engine import REDUCED_DENSITY_MAX_ROWS, check_keep, reduced_density_dm, sites_of_dim
+
+            dim = self.shape[0]
+            sites = check_keep(keep, sites_of_dim(dim, d))
+            if d ** len(sites) <= REDUCED_DENSITY_MAX_ROWS and t.numel() == dim * dim:
+                return QState(reduced_density_dm(t.reshape(1, 1, dim, dim), sites, d)[0].cpu().numpy())
+        return QState(_ptrace_host(self.full(), False, keep, d))
 
     def __repr__(self) -> str:
         where = "device tensor" if self._tensor is not None else "ket form"
@@ -540,17 +549,22 @@ class LazyState:
         return a if dtype is None else a.astype(dtype)
 
     def ptrace(self, keep: Any, local_dim: int = 2) -> QState:
-        """``QState.ptrace`` of this state.  A ket that is still a snapshot on a GPU is traced there
-        (``engine.reduced_density``, at most 64 rows): the state stays a snapshot, the call is no read of the store and
-        only the matrix crosses PCIe.  Anything else takes the host formula on the materialised state."""
-        from .engine import REDUCED_DENSITY_MAX_ROWS, check_keep, reduced_density, sites_of_dim
+        """``QState.ptrace`` of this state.  A ket or a density matrix that is still a snapshot on a GPU is traced there
+        (``engine.reduced_density`` / ``engine.reduced_density_dm``, at most 64 rows): the state stays a snapshot, the
+        call is no read of the store and only the matrix crosses PCIe.  Anything else takes the host formula on the
+        materialised state."""
+        from .engine import REDUCED_DENSITY_MAX_ROWS, check_keep, reduced_density, reduced_density_dm, sites_of_dim
 
         dev = self.device_tensor
-        if self._q is None and self.isket and dev is not None and getattr(dev, "is_cuda", False) and dev.dim() == 1 \
-                and int(local_dim) in (2, 3, 4):
+        if self._q is None and dev is not None and getattr(dev, "is_cuda", False) and int(local_dim) in (2, 3, 4) \
+                and (dev.dim() == 1 if self.isket else
+                     _is_gpu_tensor(dev) and dev.dim() == 2 and tuple(dev.shape) == self._shape
+                     and dev.is_contiguous()):  # (anything else: the host formula, not the wrapper's refusal)
             sites = check_keep(keep, sites_of_dim(self._shape[0], int(local_dim)))
             if int(local_dim) ** len(sites) <= REDUCED_DENSITY_MAX_ROWS:
-                return QState(reduced_density(dev.reshape(1, 1, -1), sites, int(local_dim))[0].cpu().numpy())
+                if self.isket:
+                    return QState(reduced_density(dev.reshape(1, 1, -1), sites, int(local_dim))[0].cpu().numpy())
+                return QState(reduced_density_dm(dev[None, None], sites, int(local_dim))[0].cpu().numpy())
         return self._materialise().ptrace(keep, local_dim)
 
     def __getattr__(self, name: str) -> Any:  # full, dag, diag, tr, norm, unit, overlap, copy, conj, T, real, ...
@@ -587,6 +601,42 @@ class LazyState:
         locals()[f"__{_n}__"] = _lazy_binary(f"__{_n}__")
         locals()[f"__r{_n}__"] = _lazy_binary(f"__r{_n}__")
     del _n
+
+
+def _is_gpu_tensor(t: Any) -> bool:
+    """A torch tensor on a GPU (a host stand-in that merely says ``is_cuda`` is none)."""
+    if not getattr(t, "is_cuda", False):
+        return False
+    import torch
+
+    return isinstance(t, torch.Tensor)
+
+
+def _live_snapshots(states: Sequence[Any], isket: bool, tail: tuple[int, ...]) -> "tuple[list[int], Any] | None":
+    """The states of ``states`` that are still snapshots (kets or density matrices, by ``isket``) of ONE store on a GPU
+    - that of the first such state, and its index on the store's second axis - as one tensor ``[T', *tail]`` over the
+    store's tensor ``[T, B, *tail]``: a strided view when they are consecutive or every k-th time, else a gathered
+    copy.  Returns their positions in ``states`` and the tensor, or None when there is none (no live snapshot of
+    that kind, a store on the host, another element shape).  Nothing is read from the store."""
+    live = [st for st in states if isinstance(st, LazyState) and st._q is None and st.isket == isket
+            and st._store is not None and st._store.device_tensor is not None]
+    if not live:
+        return None
+    store, b = live[0]._store, live[0]._b
+    dev = store.device_tensor
+    if not (getattr(dev, "is_cuda", False) and dev.dim() == 2 + len(tail) and tuple(dev.shape[2:]) == tail):
+        return None
+    if not isket and not (_is_gpu_tensor(dev) and dev[0, 0].is_contiguous()):
+        return None  # (a host stand-in, or matrices that are not row-major and dense: the host formula)
+    pos = [i for i, st in enumerate(states) if isinstance(st, LazyState) and st._q is None
+           and st._store is store and st._b == b]
+    idx = np.array([states[i]._i for i in pos], dtype=np.int64)
+    step = int(idx[1] - idx[0]) if len(idx) > 1 else 1
+    if len(idx) == 1 or (step >= 1 and np.all(np.diff(idx) == step)):  # a strided view, no copy
+        return pos, dev[int(idx[0]):int(idx[-1]) + 1:step, b]
+    import torch
+
+    return pos, dev[torch.from_numpy(idx).to(dev.device), b]
 
 
 def multinomial(n_samples: int, probabilities: np.ndarray) -> np.ndarray:
@@ -1039,15 +1089,16 @@ class SimulationResults(collections.abc.Sequence):
         significant digit) at every evaluation time: ``[len(self), dA, dA]`` complex, ``dA = dim**len(keep)`` with the
         local dimension of the run's basis.  ``normalize=True`` divides each matrix by its trace.
 
-        The states that are still ket snapshots of one store on a GPU are traced there in ONE ``engine.reduced_density``
-        call over the store's tensor (a strided view when they are consecutive or every k-th time, else a gathered
-        copy): nothing counts as a read of the store and only the matrices cross PCIe.  The host formula serves the
-        rest - the initial state, states read earlier, density matrices, ``dA`` above 64.  States of a quantum-jump
-        ensemble (``EnsembleState``) answer for the subsystems registered with ``run(mc_ensemble_subsystems=...)``
-        and refuse any other."""
+        The states that are still snapshots of one store on a GPU - kets, or the density matrices of a master-equation
+        run - are traced there in ONE ``engine.reduced_density`` / ``engine.reduced_density_dm`` call over the store's
+        tensor (a strided view when they are consecutive or every k-th time, else a gathered copy): nothing counts as
+        a read of the store and only the matrices cross PCIe.  A ``DeviceState`` (master-equation runs of 13+ atoms)
+        is traced on the device too, one call per state.  The host formula serves the rest - the initial state, states
+        read earlier, spilled stores, ``dA`` above 64.  States of a quantum-jump ensemble (``EnsembleState``) answer
+        for the subsystems registered with ``run(mc_ensemble_subsystems=...)`` and refuse any other."""
         if self._use_pseudo_dens:
             raise NotImplementedError("reduced_states() is not available for results that hold samples only")
-        from .engine import REDUCED_DENSITY_MAX_ROWS, check_keep, reduced_density
+        from .engine import REDUCED_DENSITY_MAX_ROWS, check_keep, reduced_density, reduced_density_dm
 
         d = self._dim
         sites = check_keep(keep, self._size)
@@ -1055,26 +1106,16 @@ class SimulationResults(collections.abc.Sequence):
         states = self.states
         out = np.empty((len(states), d_a, d_a), dtype=complex)
         done = [False] * len(states)
-        live = [st for st in states if isinstance(st, LazyState) and st._q is None and st.isket and st._store is not None
-                and st._store.device_tensor is not None]
-        if live and d_a <= REDUCED_DENSITY_MAX_ROWS and d in (2, 3, 4):
-            store, b = live[0]._store, live[0]._b
-            dev = store.device_tensor
-            if getattr(dev, "is_cuda", False) and dev.dim() == 3 and int(dev.shape[2]) == d ** self._size:
-                pos = [i for i, st in enumerate(states) if isinstance(st, LazyState) and st._q is None
-                       and st._store is store and st._b == b]
-                idx = np.array([states[i]._i for i in pos], dtype=np.int64)
-                step = int(idx[1] - idx[0]) if len(idx) > 1 else 1
-                if len(idx) == 1 or (step >= 1 and np.all(np.diff(idx) == step)):  # a strided view, no copy
-                    x = dev[int(idx[0]):int(idx[-1]) + 1:step, b]
-                else:
-                    import torch
-
-                    x = dev[torch.from_numpy(idx).to(dev.device), b]
-                host = reduced_density(x.unsqueeze(1), sites, d).cpu().numpy()
-                for k, i in enumerate(pos):
-                    out[i] = host[k]
-                    done[i] = True
+        if d_a <= REDUCED_DENSITY_MAX_ROWS and d in (2, 3, 4):
+            dim = d ** self._size
+            for isket, tail, trace in ((True, (dim,), reduced_density), (False, (dim, dim), reduced_density_dm)):
+                found = _live_snapshots(states, isket, tail)
+                if found is not None:
+                    pos, x = found
+                    host = trace(x.unsqueeze(1), sites, d).cpu().numpy()
+                    for k, i in enumerate(pos):
+                        out[i] = host[k]
+                        done[i] = True
         for i, st in enumerate(states):
             if not done[i]:
                 out[i] = np.asarray(st.ptrace(sites, d) if hasattr(st, "ptrace") else QState(st).ptrace(sites, d))
