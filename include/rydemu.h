@@ -367,8 +367,22 @@ int ryd_general_mc_solve_many(ryd_handle** hs, int32_t n, void* const* states_de
  * 1048576 = k_split_reg: the last run of a stretch, the double step of the step-size check behind it and its two regular
  * sub-steps as segments of ONE launch (k_split_reg_seg).  The one bit that is ON in a handle this routine has never been
  * called for: a call without it restores the launches of their own; the kets are bit for bit the same either way.
+ * 2097152 = k_split_reg: sequences whose atoms all see one drive and one detuning (ryd_desc_uniform) run the uniform
+ * kernels (k_split_reg_uni, k_split_reg_seg_uni: one coefficient record per sequence and stage).  ON in a handle this
+ * routine has never been called for, like 1048576: a call without it restores the general kernels and the record per atom;
+ * the kets then differ by rounding only (the lane's detuning sum is a product instead of a chain of additions).
  * Never needed for results. */
 int ryd_set_path(ryd_handle* h, int32_t force_generic);
+
+/* The rule behind the uniform kernels of the register-resident split-operator path, on a descriptor table [B][N] alone (no
+ * handle, no device): *out = 1 when, for every sequence, all N rows agree in drive_series, drive_scale, det_series,
+ * det_scale, off_series and off_scale and have extra == 0, and `gauged` (the handle's drives are complex and gauged away
+ * inside the real kernels: a per-atom phase on the detuning integrals) is 0; else 0.  Per-atom detuning maps, local
+ * addressing, per-atom amplitude noise and detuning-noise term lists therefore keep the general kernels. */
+int ryd_desc_uniform(const ryd_qdesc* desc, int32_t B, int32_t N, int32_t gauged, int32_t* out);
+
+/* Launches of the uniform kernels (k_split_reg_uni, k_split_reg_seg_uni) on this handle since it was created. */
+int ryd_split_uniform_launches(const ryd_handle* h, int64_t* out);
 
 /* Replaces: QobjEvo.__call__(t) applied to a state (used by
  * qutip_backend.py:259-264 and QutipOperator.apply_to, qutip_op.py:85-100).

@@ -106,6 +106,8 @@ SYMBOLS = {
                                C.POINTER(RydOpts), C.c_void_p]),
     "ryd_mc_get_jumps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ryd_set_path": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ryd_desc_uniform": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ryd_split_uniform_launches": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ryd_general_create": (C.c_int, [C.POINTER(RydGeneralConfig), C.POINTER(C.c_void_p)]),
     "ryd_general_add_term": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double]),

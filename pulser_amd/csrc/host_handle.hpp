@@ -95,7 +95,7 @@ struct ryd_handle {
   size_t ksched_cap = 0;
   // split-operator ket path (host_split.hpp)
   std::vector<Pass> split_tilings;
-  double* split_coefs = nullptr;  // [stages][B][N][4]
+  double* split_coefs = nullptr;  // [stages][B][N][4]; a launch of the uniform kernels: [stages][B][4] at its head
   size_t split_cap = 0;
   double* split_err = nullptr;    // [B] local-error accumulators
   cplx* rows_chk = nullptr;       // [2][B][2^N]: the probed rows of the split-operator master equation (rows_split_probe)
@@ -115,6 +115,12 @@ struct ryd_handle {
                                   // snapshot taken inside the run
   bool no_check_segments = false; // test / bench hook: the step-size check of k_split_reg in launches of its own instead of
                                   // as segments of the launch that ends the stretch before it (run_split)
+  // k_split_reg_uni: one coefficient record per sequence and stage where every atom of a sequence has the same drive and
+  // detuning (a Global channel).  desc_uniform: what the descriptor table says (ryd_set_qubit_desc: split_desc_uniform below);
+  // the handle takes the uniform kernels when it also is not gauged and the switch is on - uniform_atoms(), host_split.hpp
+  bool desc_uniform = false;
+  bool no_uniform_drive = false;  // test / bench hook: the general kernels and the record per atom (A/B)
+  long long n_uniform_launches = 0;  // launches of k_split_reg_uni / k_split_reg_seg_uni (ryd_split_uniform_launches)
   // ryd_set_snapshot_map: [B][snap_map_slots] ket offsets into ryd_solve's out_dev (device), or null (dense slots)
   long long* snap_map_dev = nullptr;
   int snap_map_slots = 0;
@@ -597,6 +603,34 @@ extern "C" int ryd_set_series(ryd_handle* h, int32_t n_series, int32_t n_knots,
   return RYD_OK;
 }
 
+// Do all N atoms of every sequence have the same coefficients?  (k_split_reg_uni: one record per sequence and stage)
+static bool split_desc_uniform(const ryd_qdesc* desc, int B, int N) {
+  for (int b = 0; b < B; ++b) {
+    const ryd_qdesc& a = desc[(size_t)b * N];
+    for (int k = 0; k < N; ++k) {
+      const ryd_qdesc& d = desc[(size_t)b * N + k];
+      if (d.extra != 0) return false;
+      // (scales compared as numbers: -0.0 == 0.0 is the same coefficient, a NaN is no one's)
+      if (d.drive_series != a.drive_series || d.det_series != a.det_series || d.off_series != a.off_series ||
+          !(d.drive_scale == a.drive_scale) || !(d.det_scale == a.det_scale) || !(d.off_scale == a.off_scale))
+        return false;
+    }
+  }
+  return true;
+}
+
+extern "C" int ryd_desc_uniform(const ryd_qdesc* desc, int32_t B, int32_t N, int32_t gauged, int32_t* out) {
+  if (!desc || !out || B < 1 || N < 1) return fail(RYD_ERR_INVALID, "null argument / empty table");
+  *out = (!gauged && split_desc_uniform(desc, B, N)) ? 1 : 0;
+  return RYD_OK;
+}
+
+extern "C" int ryd_split_uniform_launches(const ryd_handle* h, int64_t* out) {
+  if (!h || !out) return fail(RYD_ERR_INVALID, "null argument");
+  *out = h->n_uniform_launches;
+  return RYD_OK;
+}
+
 extern "C" int ryd_set_qubit_desc(ryd_handle* h, const ryd_qdesc* desc) {
   if (!h || !desc) return fail(RYD_ERR_INVALID, "null argument");
   if (h->n_series == 0) return fail(RYD_ERR_STATE, "ryd_set_series must be called first");
@@ -609,6 +643,7 @@ extern "C" int ryd_set_qubit_desc(ryd_handle* h, const ryd_qdesc* desc) {
   }
   HIPCHK(hipSetDevice(h->cfg.device));
   h->desc_host.assign(desc, desc + cnt);
+  h->desc_uniform = split_desc_uniform(desc, h->B, h->N);
   if (!h->desc_dev) HIPCHK(hipMalloc((void**)&h->desc_dev, cnt * sizeof(ryd_qdesc)));
   HIPCHK(hipMemcpy(h->desc_dev, desc, cnt * sizeof(ryd_qdesc), hipMemcpyHostToDevice));
   h->bounds_valid = false;

@@ -211,9 +211,35 @@ static int device_cu_count(int dev) {
   return n_cu;
 }
 
+// the dev switch RYD_SPLIT_NR asks for another register shape than the segment kernel and the uniform kernels are built for
+static bool split_reg_plain_shape_forced() { return dev_env_int("RYD_SPLIT_NR", 0, 4, 6) != 0; }
+
+// k_split_reg_uni / k_split_reg_seg_uni: one coefficient record per sequence and stage.  RYD_SPLIT_UNI=0 (dev A/B,
+// RYD_DEV=1): the general kernels
+static bool split_uni_env() {
+  static const bool on = dev_env_flag("RYD_SPLIT_UNI", true);
+  return on;
+}
+// Does this handle take the uniform kernels where it would take the plain real-drive ones?  (What the descriptor table says,
+// real drives - a gauged complex drive puts a per-atom phase on the detuning integrals -, no quantum jumps, the switch.)
+static bool uniform_atoms(const ryd_handle* h) {
+  return h->desc_uniform && h->drive_real && !h->mc && !h->no_uniform_drive && split_uni_env() && !split_reg_plain_shape_forced();
+}
+// the coefficient launch of a closed run / a launch with segments: `uni` = the records of uniform_atoms() handles
+static int launch_split_coefs(ryd_handle* h, const SplitRun& R, int n_records, bool uni, hipStream_t st) {
+  const int total = h->B * h->N;
+  hipLaunchKernelGGL(k_split_coefs, dim3((h->dterms_dev && !uni) ? (total + 3) / 4 : (total + 255) / 256, n_records), dim3(256), 0, st,
+                     h->pp_dev, h->n_knots - 1, h->desc_dev, h->dterms_dev, total, R, h->split_coefs, uni ? h->N : 0);
+  HIPCHK(hipGetLastError());
+  return RYD_OK;
+}
+
 template <int N>
-static int launch_split_reg(ryd_handle* h, const SplitArgs& A, const SplitRun& R, hipStream_t st, size_t n_rows = 0, bool snap = false) {
+static int launch_split_reg(ryd_handle* h, const SplitArgs& A, const SplitRun& R, hipStream_t st, size_t n_rows = 0, bool snap = false,
+                            bool uni = false) {
   constexpr int NT = 64 << (N - 11);
+  if (uni && (n_rows || snap || h->mc || !split_real(h) || split_reg_plain_shape_forced()))
+    return fail(RYD_ERR_STATE, "split-operator run: uniform coefficient records on a run the plain kernel would not take");
   // RYD_SPLIT_NR (dev A/B, RYD_DEV=1): 6 = 64 amplitudes per lane on 256 lanes (14 atoms only; measured slower), 4 / 5 at
   // 12 atoms = force the shape below
   static const int nr_env = dev_env_int("RYD_SPLIT_NR", 0, 4, 6);
@@ -230,7 +256,10 @@ static int launch_split_reg(ryd_handle* h, const SplitArgs& A, const SplitRun& R
       const size_t lds4 = (size_t)2 * NT4 * 4 * 16 + SPLITR_TRIG * 16 + (size_t)(NT4 / 64) * splitr_gtab_slots<12, 4>(false, false, false, false) * 16 +
                           (SPLIT_MAX_SUB * SPLIT_MAX_STAGES + 2) * 8 + (SPLITR_EMODE ? 4 * NT4 * 8 : 0) + (128 + 32) * 8;
       const long long stride4 = (long long)h->B * N * 4;
-      if (snap)
+      if (uni) {
+        hipLaunchKernelGGL((k_split_reg_uni<12, 4>), dim3(1, h->B), dim3(NT4), lds4, st, A, R, (long long)h->B * 4);
+        h->n_uniform_launches++;
+      } else if (snap)
         hipLaunchKernelGGL((k_split_reg<12, 4, false, false, false, true>), dim3(1, h->B), dim3(NT4), lds4, st, A, R, stride4);
       else
         hipLaunchKernelGGL((k_split_reg<12, 4, false>), dim3(1, h->B), dim3(NT4), lds4, st, A, R, stride4);
@@ -254,6 +283,8 @@ static int launch_split_reg(ryd_handle* h, const SplitArgs& A, const SplitRun& R
     HIPCHK(hipFuncSetAttribute((const void*)k_split_reg<N, 5, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     if constexpr (N == 14)
       HIPCHK(hipFuncSetAttribute((const void*)k_split_reg<14, 6, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if constexpr (N != 12)
+      HIPCHK(hipFuncSetAttribute((const void*)k_split_reg_uni<N, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     if (dev >= 0 && dev < 64) attr[dev] = true;
   }
   const long long stride = (long long)h->B * N * 4;
@@ -278,19 +309,21 @@ static int launch_split_reg(ryd_handle* h, const SplitArgs& A, const SplitRun& R
   else if (N == 14 && nr_env == 6) {
     if constexpr (N == 14)
       hipLaunchKernelGGL((k_split_reg<14, 6, false>), dim3(1, h->B), dim3(256), lds, st, A, R, stride);
+  } else if (uni) {
+    if constexpr (N != 12) {
+      hipLaunchKernelGGL((k_split_reg_uni<N, 5>), dim3(1, h->B), dim3(NT), lds_x, st, A, R, (long long)h->B * 4);
+      h->n_uniform_launches++;
+    }
   } else
     hipLaunchKernelGGL((k_split_reg<N, 5, false>), dim3(1, h->B), dim3(NT), lds_x, st, A, R, stride);
   HIPCHK(hipGetLastError());
   return RYD_OK;
 }
 
-// the dev switch RYD_SPLIT_NR asks for another register shape than the segment kernel is built for
-static bool split_reg_plain_shape_forced() { return dev_env_int("RYD_SPLIT_NR", 0, 4, 6) != 0; }
-
 // k_split_reg_seg: the plain real-drive ket kernel over the segments of R, in the shape (and with the LDS) launch_split_reg
 // gives the plain kernel of that register size
 template <int N>
-static int launch_split_reg_seg(ryd_handle* h, const SplitArgs& A, const SplitRun& R, hipStream_t st) {
+static int launch_split_reg_seg(ryd_handle* h, const SplitArgs& A, const SplitRun& R, hipStream_t st, bool uni = false) {
   constexpr int NR = N == 12 ? 4 : 5;
   constexpr int NT = 64 << (N - 6 - NR);
   constexpr int CH = (1 << NR) / 4;
@@ -300,9 +333,14 @@ static int launch_split_reg_seg(ryd_handle* h, const SplitArgs& A, const SplitRu
   static bool attr[64] = {};
   if (lds > 64 * 1024 && (dev < 0 || dev >= 64 || !attr[dev])) {
     HIPCHK(hipFuncSetAttribute((const void*)k_split_reg_seg<N, NR>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void*)k_split_reg_seg_uni<N, NR>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     if (dev >= 0 && dev < 64) attr[dev] = true;
   }
-  hipLaunchKernelGGL((k_split_reg_seg<N, NR>), dim3(1, h->B), dim3(NT), lds, st, A, R, (long long)h->B * N * 4);
+  if (uni) {
+    hipLaunchKernelGGL((k_split_reg_seg_uni<N, NR>), dim3(1, h->B), dim3(NT), lds, st, A, R, (long long)h->B * 4);
+    h->n_uniform_launches++;
+  } else
+    hipLaunchKernelGGL((k_split_reg_seg<N, NR>), dim3(1, h->B), dim3(NT), lds, st, A, R, (long long)h->B * N * 4);
   HIPCHK(hipGetLastError());
   return RYD_OK;
 }
@@ -401,13 +439,12 @@ static int split_run(ryd_handle* h, cplx* buf, const SubStep* subs, int nsub, hi
   for (int s = 0; s < nsub; ++s) { R.idx[s] = subs[s].idx; R.u0[s] = subs[s].u0; R.tau[s] = subs[s].tau; }
   R.tan_form = reg_loop ? (split_real(h) ? 1 : 2) : ((loop14 || pass_tan) && split_real(h) ? 1 : 0);
   R.gauge = split_gauged(h) ? 1 : 0;
-  const int total = B * N;
   // (+ one closing record per sub-step when snapshots are taken inside the run: k_split_snap_close)
   const int n_records = n_stages + (any_inner ? nsub : 0);
   if (any_inner && (rc = split_ensure_tables(h, n_records))) return rc;
-  hipLaunchKernelGGL(k_split_coefs, dim3(h->dterms_dev ? (total + 3) / 4 : (total + 255) / 256, n_records), dim3(256), 0, st,
-                     h->pp_dev, h->n_knots - 1, h->desc_dev, h->dterms_dev, total, R, h->split_coefs);
-  HIPCHK(hipGetLastError());
+  // one record per sequence where the run is one of the plain real-drive kernel and the atoms of a sequence are alike
+  const bool uni = reg_loop && !any_inner && split_real(h) && uniform_atoms(h);
+  if ((rc = launch_split_coefs(h, R, n_records, uni, st))) return rc;
 
   // weight of E0 in the D of every stage (the pass-by-pass launches; k_split_reg builds its own table)
   std::vector<double> wE(n_stages);
@@ -456,8 +493,8 @@ static int split_run(ryd_handle* h, cplx* buf, const SubStep* subs, int nsub, hi
     }
     std::pair<hipEvent_t, hipEvent_t> ev1;
     if (h->timing) { if ((rc = timing_begin(h, st, ev1))) return rc; }
-    rc = N == 14 ? launch_split_reg<14>(h, A, R, st, 0, any_inner) : N == 13 ? launch_split_reg<13>(h, A, R, st, 0, any_inner)
-                                                                              : launch_split_reg<12>(h, A, R, st, 0, any_inner);
+    rc = N == 14 ? launch_split_reg<14>(h, A, R, st, 0, any_inner, uni) : N == 13 ? launch_split_reg<13>(h, A, R, st, 0, any_inner, uni)
+                                                                                   : launch_split_reg<12>(h, A, R, st, 0, any_inner, uni);
     if (rc) return rc;
     if (h->timing) { HIPCHK(hipEventRecord(ev1.second, st)); h->ev_used.push_back(ev1); }
     h->stats.n_launches++;
@@ -748,10 +785,7 @@ static int rows_split_pass(ryd_handle* h, cplx* buf, const std::vector<StepDesc>
     R.kick_u = kick_u;
     const int n_stages = sc.S * nsub + 1 + (R.kick_pre != 0.0 ? 1 : 0);
     if ((rc = split_ensure_tables(h, n_stages))) return rc;
-    const int total = B * N;
-    hipLaunchKernelGGL(k_split_coefs, dim3(h->dterms_dev ? (total + 3) / 4 : (total + 255) / 256, n_stages), dim3(256), 0, st,
-                       h->pp_dev, h->n_knots - 1, h->desc_dev, h->dterms_dev, total, R, h->split_coefs);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch_split_coefs(h, R, n_stages, false, st))) return rc;
     SplitArgs A;
     std::memset(&A, 0, sizeof A);
     A.state = buf;
@@ -860,10 +894,8 @@ static int split_run_segments(ryd_handle* h, cplx* state, const std::vector<SubS
   ++q;
   R.seg_end[q] = nsub;
   R.seg_flags[q] = SPLIT_SEG_CMP;  // the regular sub-steps: in place, compared with wA, the new checkpoint into wC
-  const int total = B * N;
-  hipLaunchKernelGGL(k_split_coefs, dim3(h->dterms_dev ? (total + 3) / 4 : (total + 255) / 256, n_records), dim3(256), 0, st,
-                     h->pp_dev, h->n_knots - 1, h->desc_dev, h->dterms_dev, total, R, h->split_coefs);
-  HIPCHK(hipGetLastError());
+  const bool uni = uniform_atoms(h);  // (split_mixes above: the plain real-drive kernel, no quantum jumps)
+  if ((rc = launch_split_coefs(h, R, n_records, uni, st))) return rc;
   SplitArgs A;
   std::memset(&A, 0, sizeof A);
   A.state = state;
@@ -880,7 +912,7 @@ static int split_run_segments(ryd_handle* h, cplx* state, const std::vector<SubS
   A.cmp_err = h->split_err_pin_dev;
   std::pair<hipEvent_t, hipEvent_t> ev1;
   if (h->timing) { if ((rc = timing_begin(h, st, ev1))) return rc; }
-  rc = N == 14 ? launch_split_reg_seg<14>(h, A, R, st) : N == 13 ? launch_split_reg_seg<13>(h, A, R, st) : launch_split_reg_seg<12>(h, A, R, st);
+  rc = N == 14 ? launch_split_reg_seg<14>(h, A, R, st, uni) : N == 13 ? launch_split_reg_seg<13>(h, A, R, st, uni) : launch_split_reg_seg<12>(h, A, R, st, uni);
   if (rc) return rc;
   if (h->timing) { HIPCHK(hipEventRecord(ev1.second, st)); h->ev_used.push_back(ev1); }
   h->stats.n_launches++;

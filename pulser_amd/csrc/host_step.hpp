@@ -789,6 +789,9 @@ extern "C" int ryd_set_path(ryd_handle* h, int32_t force_generic) {
     // k_split_reg: a stretch and its step-size check as segments of one launch - what a handle does until this routine is
     // called; a call WITHOUT the bit restores the launches of their own (A/B: Engine.set_path(check_segments=False))
     h->no_check_segments = (force_generic & 1048576) == 0;
+    // k_split_reg_uni for sequences of identical atoms - likewise on until a call WITHOUT the bit (A/B:
+    // Engine.set_path(uniform_drive=False): the general kernels, one coefficient record per atom)
+    h->no_uniform_drive = (force_generic & 2097152) == 0;
     {
       const bool s6 = (force_generic & 8192) != 0;  // split-operator passes: S6, sub-steps end at every knot
       if (s6 != h->split_s6_only) { h->split_s6_only = s6; h->split_known = false; }

@@ -26,11 +26,18 @@
 __global__ __launch_bounds__(256) void k_split_coefs(const cplx* __restrict__ pp, int n_int,
                                                      const ryd_qdesc* __restrict__ desc,
                                                      const ryd_dterm* __restrict__ dterms, int total,
-                                                     const SplitRun R, double* __restrict__ out) {
+                                                     const SplitRun R, double* __restrict__ out, const int uni) {
   // one wave per (trajectory, atom) when extra detuning terms have to be summed (high-frequency noise); one LANE per
   // (trajectory, atom) otherwise (dterms == nullptr: 256 items per workgroup - the wave-per-item launch of the 256 x
   // 14-atom batch took 205 us per closed run, 8 % of the bench step)
-  const bool per_lane = dterms == nullptr;
+  // uni = N (k_split_reg_uni: every atom of a sequence has the same coefficients, ryd_handle.desc_uniform; else 0): the
+  // launch is the general one - an item per (record, sequence, atom), the arithmetic per field the general one - but ONE
+  // record per sequence is stored, [record][B][4] = (C^N, Im g / C, Im g, Delta), by the item of atom 0: the stage's cosine
+  // product is formed here, multiplied up in the order the general kernel's stage does it.
+  // (A launch with one item per (record, sequence) was measured too: 7.2 instead of 14.3 us per launch, -0.21 ms on the
+  // headline step but -0.14 ms on cfg2, less than 3 x the parent's spread there - profiles/uniform_drive.md.)
+  const int un = uni;
+  const bool per_lane = dterms == nullptr || uni != 0;
   const int i = per_lane ? (int)(blockIdx.x * 256 + threadIdx.x) : (int)(blockIdx.x * 4 + (threadIdx.x >> 6));
   const int lane = per_lane ? 0 : (int)(threadIdx.x & 63);
   if (i >= total) return;
@@ -52,8 +59,10 @@ __global__ __launch_bounds__(256) void k_split_coefs(const cplx* __restrict__ pp
         C = cs;
         gi = -sn;
       }
-      double* o = out + ((size_t)blockIdx.y * total + i) * 4;
+      if (uni && i % un != 0) return;
+      double* o = out + ((size_t)blockIdx.y * (uni ? total / un : total) + (uni ? i / un : i)) * 4;
       o[0] = C;
+      if (uni) { double p = 1.0; for (int k = 0; k < un; ++k) p *= C; o[0] = p; }
       o[1] = R.tan_form ? gi / C : 0.0;
       o[2] = gi;
       o[3] = 0.0;
@@ -144,8 +153,10 @@ __global__ __launch_bounds__(256) void k_split_coefs(const cplx* __restrict__ pp
     }
     if (R.tan_form == 1) gr = gi / C;  // (real drives: gr was 0; the host keeps |beta c| <= 1, so C >= 0.54)
     else if (R.tan_form == 2) { gr /= C; gi /= C; }  // complex drives on k_split_reg<.., CPLX>: both parts over C
-    double* o = out + ((size_t)blockIdx.y * total + i) * 4;
+    if (uni && i % un != 0) return;
+    double* o = out + ((size_t)blockIdx.y * (uni ? total / un : total) + (uni ? i / un : i)) * 4;
     o[0] = C;
+    if (uni) { double p = 1.0; for (int k = 0; k < un; ++k) p *= C; o[0] = p; }
     o[1] = gr;
     o[2] = gi;
     o[3] = dl;

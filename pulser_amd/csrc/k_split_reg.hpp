@@ -297,10 +297,18 @@ __device__ __forceinline__ double splitr_partner(double v) {
 // the stretch has just stored) and the two regular sub-steps the check compares it with.  The trig table, the stage weights
 // of all segments and the E0 pieces are set up once; the segment loop is the row loop of ROWS, and the stage body is the one
 // of the plain kernel.  The kernel without segments is a separate instantiation of the same body and does not change.
-template <int N, int NR, bool DECAY, bool ROWS, bool CPLX, bool SNAP, bool SEG>
+// UNI (k_split_reg_uni, k_split_reg_seg_uni below; plain real-drive kets only): every atom of a sequence has the same drive
+// and the same detuning (a Global channel: ryd_handle.desc_uniform), and the sequence's coefficients of a stage are ONE
+// record of 32 bytes, [record][B][4] = (C^N, Im g / C, Im g, Delta) - k_split_coefs in its uniform mode: one scalar load per
+// stage instead of 14 x (C, T, Delta), every position's T and Delta the same scalar, the cosine product of the stage read
+// instead of multiplied up, and the lane's detuning sum Delta x (the number of its atoms in the excited state - a per-lane
+// constant of the prologue) instead of a chain of selects and additions.  Everything else is the one stage body.
+template <int N, int NR, bool DECAY, bool ROWS, bool CPLX, bool SNAP, bool SEG, bool UNI = false>
 __device__ __forceinline__ void split_reg_body(const SplitArgs& A, const SplitRun& R, const long long stage_stride) {
   static_assert(!(SNAP && (ROWS || DECAY)), "snapshots inside a run: plain ket runs only");
   static_assert(!(SEG && (ROWS || DECAY || CPLX || SNAP)), "segments: plain real-drive ket runs only");
+  static_assert(!(UNI && (ROWS || DECAY || CPLX || SNAP)), "one record per sequence: plain real-drive ket runs only");
+  static_assert(!(UNI && (SPLITR_PREF || SPLITR_LATE_REAL)), "one record per sequence: loaded where the stage starts");
   // (the prefetch of the next stage's record starts at record 0 and flips the parity at every stage: it knows neither where a
   // segment starts nor that the closing stage keeps the layout)
   static_assert(!(SEG && SPLITR_PREF), "segments: SPLITR_PREF is not carried across segment boundaries");
@@ -337,7 +345,7 @@ __device__ __forceinline__ void split_reg_body(const SplitArgs& A, const SplitRu
   // (SplitArgs.conj: conj(U) psi = conj(U conj(psi)) - the ket is conjugated at the load and at the store, the stages
   // in between are the ordinary ones: nothing in the stage loop knows about it)
   const double csgn = (ROWS && A.conj) ? -1.0 : 1.0;
-  const double* __restrict__ coefs = A.ccur + (size_t)b * N * 4;
+  const double* __restrict__ coefs = A.ccur + (size_t)b * (UNI ? 1 : N) * 4;
   const double* __restrict__ e0 = A.e0 + (size_t)b * A.e0_stride;
 
   if (SPLITR_WMODE) {
@@ -408,7 +416,7 @@ __device__ __forceinline__ void split_reg_body(const SplitArgs& A, const SplitRu
   auto expmi_fin = [&](double rr, cplx tb) -> cplx {
     const double r2 = rr * rr;
     double cr, sr;
-    if (SPLITR_TRIG >= 512) {  // |rr| <= pi / 512: the next terms are below 1e-19
+    if (SPLITR_TRIG >= 512) {  // |rr| <= pi / 512: the next terms are r^6 / 720 <= 7e-17 (cosine) and r^7 / 5040 <= 6e-20 (sine)
       cr = fma(r2, fma(r2, 4.1666666666666664e-02, -0.5), 1.0);
       sr = rr * fma(r2, fma(r2, 8.333333333333333e-03, -1.6666666666666666e-01), 1.0);
     } else {
@@ -427,6 +435,15 @@ __device__ __forceinline__ void split_reg_body(const SplitArgs& A, const SplitRu
   cplx* __restrict__ const tslice = pbuf + 64 * w;
   const unsigned la = l & ((1u << ND) - 1u), lT = l >> ND;
 
+  // UNI: the number of the lane's own atoms whose detuning integral joins B's argument (the clear bits among its DPP lane
+  // bits and wave bits; SPLITR_XPASS: lane bits 4, 5 always bring one - their own atom's or the T-position partner's)
+  double n_t = 0.0;
+  if constexpr (UNI) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) n_t += (kX && j >= ND) ? 1.0 : (((tq >> j) & 1u) ? 0.0 : 1.0);
+#pragma unroll
+    for (int j = 0; j < NW; ++j) n_t += ((tq >> (6 + j)) & 1u) ? 0.0 : 1.0;
+  }
   double xr[NA], xi[NA];  // (outside the loop: a segment may go on from the registers of the one before it)
   // (SEG: `row` counts the segments)
   for (unsigned row = ROWS ? blockIdx.y : 0u; row < (ROWS ? (1u << N) : SEG ? (unsigned)R.nseg : 1u); row += ROWS ? gridDim.y : 1u) {
@@ -521,13 +538,39 @@ __device__ __forceinline__ void split_reg_body(const SplitArgs& A, const SplitRu
     // complex drives only AFTER the phase factors (SPLITR_LATE: the pointer is laundered through an empty asm so that
     // the loads cannot be hoisted): 14 x (C, Re g / C, Im g / C) on top of the 14 integrals do not fit the scalar
     // registers (79 spilled, and a spilled scalar load is a serialised one: +1 us per stage, round-4 variants table)
+    // UNI: the sequence's record of this stage, one scalar load of 32 bytes
+    typedef double splitr_rec_t __attribute__((ext_vector_type(4)));
+    splitr_rec_t rec = {1.0, 0.0, 0.0, 0.0};
+    double Du = 0.0;  // its Delta
+    if constexpr (UNI) {
+      rec = *reinterpret_cast<const __attribute__((address_space(4))) splitr_rec_t*>(c4);
+      Du = rec[3];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) Dl[j] = Du;
+#pragma unroll
+      for (int j = 0; j < NW; ++j) Dw[j] = Du;
+#pragma unroll
+      for (int j = 0; j < NR; ++j) Dr[j] = Du;
+    } else {
 #pragma unroll
     for (int j = 0; j < 6; ++j) Dl[j] = SPLITR_PREF ? Dn[j] : coef(L::lanebit(false, j), L::lanebit(true, j), 3);
 #pragma unroll
     for (int j = 0; j < NW; ++j) Dw[j] = SPLITR_PREF ? Dn[6 + j] : coef(L::wavebit(false, j), L::wavebit(true, j), 3);
 #pragma unroll
     for (int j = 0; j < NR; ++j) Dr[j] = SPLITR_PREF ? Dn[6 + NW + j] : coef(L::regbit(false, j), L::regbit(true, j), 3);
+    }
     auto load_rot = [&](cptr_t cl) {
+      if constexpr (UNI) {  // one T for every position; the product of the N cosines is the record's first field
+        const double Tu = rec[TF];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) { Tl[j] = Tu; Ul[j] = 0.0; }
+#pragma unroll
+        for (int j = 0; j < NW; ++j) { Tw[j] = Tu; Uw[j] = 0.0; }
+#pragma unroll
+        for (int j = 0; j < NR; ++j) { Tr[j] = Tu; Ur[j] = 0.0; }
+        cnext = rec[0];
+        return;
+      }
       auto coefl = [&](int bit_even, int bit_odd, int field) -> double {
         const int p = odd ? bit_odd : bit_even;
         return cl[4 * (N - 1 - p) + field];
@@ -589,16 +632,16 @@ __device__ __forceinline__ void split_reg_body(const SplitArgs& A, const SplitRu
       });
     };
     if (!(SPLITR_KO & 8)) {
-      double dthr = 0.0;
+      double dthr = UNI ? Du * n_t : 0.0;
 #pragma unroll
-      for (int j = 0; j < 6; ++j) {
+      for (int j = 0; j < (UNI ? 0 : 6); ++j) {
         // (SPLITR_XPASS: a lane with bit ND + m set holds the atom of T bit m flipped - that atom's integral joins B's argument
         // exactly where the lane's own does not: one select, one addition)
         if (kX && j >= ND) dthr += ((tq >> j) & 1u) ? Dr[NW + (j >= ND ? j - ND : 0)] : Dl[j];
         else dthr += ((tq >> j) & 1u) ? 0.0 : Dl[j];
       }
 #pragma unroll
-      for (int j = 0; j < NW; ++j) dthr += ((tq >> (6 + j)) & 1u) ? 0.0 : Dw[j];
+      for (int j = 0; j < (UNI ? 0 : NW); ++j) dthr += ((tq >> (6 + j)) & 1u) ? 0.0 : Dw[j];
       double sc = cprod;
       if (DECAY)  // H_eff: the real factor exp(wE (dec_a + dec_b popc(index))): lane part here, register part in F
         sc *= exp(wE * (A.dec_a + A.dec_b * (double)(__popc(tq) + NR)));
@@ -863,7 +906,8 @@ __device__ __forceinline__ void split_reg_body(const SplitArgs& A, const SplitRu
     // barrier; that group's rotations, pre(C0) and write_pre(C0, C1) lie in between - and are folded into `warm` only there.
     // (Shapes whose groups go through the LDS transposition issue them behind the group loop.)  The address is the scalar
     // c4 plus the stride; the touched values pass through an empty asm so that their use cannot be pulled forward.
-    unsigned wv[8];
+    constexpr int NWV = UNI ? 1 : 8;  // touches of the next record (UNI: its 32 bytes lie in one line)
+    unsigned wv[NWV];
     constexpr bool kWarmLate = (SPLITR_KWARM == 2 || SPLITR_KWARM == 3) && NW > 0 && !(SPLITR_KO & 4);
     // (complex drives issue them behind the loop too: <14, 5, DECAY, CPLX> spills a vector register otherwise)
     constexpr bool kWarmInLoop = kWarmLate && SPLITR_TMODE == 1 && NTB == 2 && !CPLX;
@@ -882,7 +926,7 @@ __device__ __forceinline__ void split_reg_body(const SplitArgs& A, const SplitRu
         // (one word per 64-byte line of the sequence's 8 N words, the last line by its last word - and never beyond it: at 12
         // atoms the record is 6 lines, line 6 is the next sequence's, and behind the last sequence of the last record the end of
         // the table - on a page boundary when the records are a multiple of 32, which a launch with segments can be)
-        for (int k = 0; k < 8; ++k) wv[k] = nx[(k < 7 && 16 * k < 8 * N) ? 16 * k : 8 * N - 1];
+        for (int k = 0; k < NWV; ++k) wv[k] = UNI ? nx[0] : nx[(k < 7 && 16 * k < 8 * N) ? 16 * k : 8 * N - 1];
       } else {
         // lane k on line k (the last line by its last word); the value of the PREVIOUS stage's touch is folded first
         warm_va ^= warm_v;
@@ -890,7 +934,7 @@ __device__ __forceinline__ void split_reg_body(const SplitArgs& A, const SplitRu
         // (the global address space by name: a generic pointer would make it a flat load, which counts on the LDS /
         // scalar counter as well)
         typedef const __attribute__((address_space(1))) unsigned* gptr_t;
-        warm_v = ((gptr_t)na)[(k < 7u && 16u * k < 8u * N) ? 16u * k : 8u * N - 1u];
+        warm_v = ((gptr_t)na)[UNI ? 0u : (k < 7u && 16u * k < 8u * N) ? 16u * k : 8u * N - 1u];
       }
       __builtin_amdgcn_sched_barrier(0);
     };
@@ -1041,7 +1085,7 @@ __device__ __forceinline__ void split_reg_body(const SplitArgs& A, const SplitRu
       write_pre(C0{}, C1{});
       if constexpr (SPLITR_KWARM == 2) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
+        for (int k = 0; k < NWV; ++k) {
           asm volatile("" : "+s"(wv[k]));
           warm ^= wv[k];
         }
@@ -1052,7 +1096,7 @@ __device__ __forceinline__ void split_reg_body(const SplitArgs& A, const SplitRu
         typedef const __attribute__((address_space(4))) unsigned* uptr_t;
         uptr_t nx = (uptr_t)(unsigned long long)(coefs + (size_t)(sg + 1 < n_stages ? sg + 1 : sg) * stage_stride);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) warm ^= nx[(k < 7 && 16 * k < 8 * N) ? 16 * k : 8 * N - 1];
+        for (int k = 0; k < NWV; ++k) warm ^= UNI ? nx[0] : nx[(k < 7 && 16 * k < 8 * N) ? 16 * k : 8 * N - 1];
       }
       write_pre(C1{}, C2{});
       __syncthreads();
@@ -1237,4 +1281,16 @@ __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per
 template <int N, int NR>
 __global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_split_reg_seg(const SplitArgs A, const SplitRun R, long long stage_stride) {
   split_reg_body<N, NR, false, false, false, false, true>(A, R, stage_stride);
+}
+
+// the same two kernels for sequences whose atoms all see one drive and one detuning (UNI above): one coefficient record of 32
+// bytes per sequence and stage (stage_stride = 4 B doubles).  Kernels of their own, not a template argument of the general
+// ones: those keep their names and their code.
+template <int N, int NR>
+__global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_split_reg_uni(const SplitArgs A, const SplitRun R, long long stage_stride) {
+  split_reg_body<N, NR, false, false, false, false, false, true>(A, R, stage_stride);
+}
+template <int N, int NR>
+__global__ __launch_bounds__(64 << (N - 6 - NR)) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_split_reg_seg_uni(const SplitArgs A, const SplitRun R, long long stage_stride) {
+  split_reg_body<N, NR, false, false, false, false, true, true>(A, R, stage_stride);
 }

@@ -27,6 +27,13 @@
 #define SPLITR_SEG_INSTANCES_14(X) X(14, 5)
 #define SPLITR_SEG_EXTERN(N_, NR_) extern template __global__ void k_split_reg_seg<N_, NR_>(const SplitArgs, const SplitRun, long long);
 #define SPLITR_SEG_DEFINE(N_, NR_) template __global__ void k_split_reg_seg<N_, NR_>(const SplitArgs, const SplitRun, long long);
+// k_split_reg_uni / k_split_reg_seg_uni<N, NR>: the same shapes for sequences with one coefficient record per stage
+#define SPLITR_UNI_EXTERN(N_, NR_)                                                                          \
+  extern template __global__ void k_split_reg_uni<N_, NR_>(const SplitArgs, const SplitRun, long long); \
+  extern template __global__ void k_split_reg_seg_uni<N_, NR_>(const SplitArgs, const SplitRun, long long);
+#define SPLITR_UNI_DEFINE(N_, NR_)                                                                   \
+  template __global__ void k_split_reg_uni<N_, NR_>(const SplitArgs, const SplitRun, long long); \
+  template __global__ void k_split_reg_seg_uni<N_, NR_>(const SplitArgs, const SplitRun, long long);
 
 #define SPLITR_EXTERN(N_, NR_, D_, R_, C_, S_) \
   extern template __global__ void k_split_reg<N_, NR_, D_, R_, C_, S_>(const SplitArgs, const SplitRun, long long);

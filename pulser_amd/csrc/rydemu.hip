@@ -69,8 +69,11 @@ SPLITR_INSTANCES_12(SPLITR_EXTERN)
 SPLITR_INSTANCES_13(SPLITR_EXTERN)
 SPLITR_INSTANCES_14(SPLITR_EXTERN)
 SPLITR_SEG_INSTANCES_12(SPLITR_SEG_EXTERN)
+SPLITR_SEG_INSTANCES_12(SPLITR_UNI_EXTERN)
 SPLITR_SEG_INSTANCES_13(SPLITR_SEG_EXTERN)
+SPLITR_SEG_INSTANCES_13(SPLITR_UNI_EXTERN)
 SPLITR_SEG_INSTANCES_14(SPLITR_SEG_EXTERN)
+SPLITR_SEG_INSTANCES_14(SPLITR_UNI_EXTERN)
 #endif
 #include "k_observe.hpp"
 #include "k_gen_observe.hpp"

@@ -26,12 +26,15 @@ typedef double2 cplx;
 #if RYD_SPLITR_N == 12
 SPLITR_INSTANCES_12(SPLITR_DEFINE)
 SPLITR_SEG_INSTANCES_12(SPLITR_SEG_DEFINE)
+SPLITR_SEG_INSTANCES_12(SPLITR_UNI_DEFINE)
 #elif RYD_SPLITR_N == 13
 SPLITR_INSTANCES_13(SPLITR_DEFINE)
 SPLITR_SEG_INSTANCES_13(SPLITR_SEG_DEFINE)
+SPLITR_SEG_INSTANCES_13(SPLITR_UNI_DEFINE)
 #elif RYD_SPLITR_N == 14
 SPLITR_INSTANCES_14(SPLITR_DEFINE)
 SPLITR_SEG_INSTANCES_14(SPLITR_SEG_DEFINE)
+SPLITR_SEG_INSTANCES_14(SPLITR_UNI_DEFINE)
 #else
 #error "rydemu_splitreg.hip: RYD_SPLITR_N must be 12, 13 or 14"
 #endif

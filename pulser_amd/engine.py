@@ -836,7 +836,7 @@ class Engine:
                  split_fixed: bool = False, split_no_loop: bool = False,
                  no_merge: bool = False, split_small_tiles: bool = False, split_s6: bool = False,
                  no_split14: bool = False, split_turns: bool = False, rows_ket: bool = False,
-                 snaps_outside: bool = False, check_segments: bool = True) -> None:
+                 snaps_outside: bool = False, check_segments: bool = True, uniform_drive: bool = True) -> None:
         """Test/bench hook: disable the persistent small-N kernel and/or the 2^14
         register-tile kernel with the Hermitian mesolve path (the tiled
         multi-pass kernels are used instead), or force the register tiles;
@@ -855,6 +855,9 @@ class Engine:
         the registers inside the run;
         ``check_segments=False``: the step-size check of k_split_reg in launches of its own (the run that ends the stretch,
         the double step, the two regular sub-steps) instead of as segments of one launch - the same kets bit for bit;
+        ``uniform_drive=False``: sequences whose atoms all see one drive and one detuning (a Global channel) run the general
+        kernels of k_split_reg with a coefficient record per atom instead of k_split_reg_uni with one per sequence - the
+        same stages and launches, kets equal up to rounding (:meth:`uniform_launches` counts the uniform launches);
         ``split_s6`` keeps the 4th-order composition with sub-steps that end at every knot
         (round 2) where the 6th-order one with multi-knot sub-steps is the default."""
         _lib.check(self.lib.ryd_set_path(
@@ -865,7 +868,14 @@ class Engine:
             | (256 if split_fixed else 0) | (512 if split_no_loop else 0)
             | (1024 if no_merge else 0) | (2048 if split_small_tiles else 0) | (8192 if split_s6 else 0)
             | (16384 if no_split14 else 0) | (32768 if split_turns else 0) | (65536 if rows_ket else 0)
-            | (131072 if snaps_outside else 0) | (1048576 if check_segments else 0)))
+            | (131072 if snaps_outside else 0) | (1048576 if check_segments else 0)
+            | (2097152 if uniform_drive else 0)))
+
+    def uniform_launches(self) -> int:
+        """Launches of the uniform kernels (k_split_reg_uni, k_split_reg_seg_uni) on this engine so far."""
+        n = C.c_int64(0)
+        _lib.check(self.lib.ryd_split_uniform_launches(self._h, C.byref(n)))
+        return int(n.value)
 
     def apply_generator(self, x: Any, t: float) -> Any:
         """``G(t) x`` with ``G = -iH`` (sesolve) or the Lindbladian (mesolve)."""
